@@ -11,6 +11,10 @@ A "step" re-enacts the reference's Trainer.train_step (train.py:442-549) on synt
 model forward -> monodepth loss -> segmentation loss -> backward -> gradient all-reduce (N>1) -> clip_grad_norm ->
 optimiser step.  Default workload = BASELINE.json configs[2]: cityscapes_joint.yml + decoder_variant(dec=6) ResNet-101
 joint_seg_depth_dec, 512x1024, per-GPU batch 16, SGD (experiments.py:32-48,139-145).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure -- per-kernel timing and
+the roofline figures built on it, the `reference_step` / `amp_step` blocks, the N>1 `comm` block, the CPU baseline -- runs
+only with --full.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -221,6 +225,54 @@ def _flush_c_stdio():
     sys.stdout.flush()
 
 
+DUMP_MAX_ELEMS = 1 << 17            # per output array: a larger one is dumped as a sample of this many elements
+DUMP_MAX_PARAM_ELEMS = 1 << 20      # the same for the concatenated parameters and gradients
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample(t, n_max, name):
+    """``t`` flattened in its logical (NCHW) order: all of it when small, else ``n_max`` elements at sorted uniform positions
+    drawn from a generator seeded with the CRC-32 of ``name`` (the same positions in every run of the same arguments)"""
+    import zlib
+    if t.numel() <= n_max:
+        return t.detach()
+    flat = t.detach().reshape(-1)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    idx = torch.randint(0, flat.numel(), (n_max,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(dirname, loss, captured, model):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float32 (``loss``: float64).
+    ``out_<key>``: every floating-point tensor the model's forward and the monodepth loss left in the step's outputs dict
+    (entries that dict computes only on access are not materialised; a --hip-graph replay has no outputs dict);
+    ``loss_<name>``: the losses trainer.train_step returns (--step reference / amp); ``params`` / ``grads``: the parameters
+    after the optimiser step and their gradients, concatenated in ``model.parameters()`` order (no gradient: zeros).
+    Arrays above the caps are a fixed seeded sample (see _sample)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"loss": np.asarray(float(loss.detach()), dtype=np.float64)}
+
+    def add(name, t):
+        while name in arrays:
+            name += "_"
+        a = _sample(t, DUMP_MAX_ELEMS if name not in ("params", "grads") else DUMP_MAX_PARAM_ELEMS, name)
+        arrays[name] = a.cpu().numpy().astype(np.float64 if a.dtype == torch.float64 else np.float32)
+
+    for prefix, d in (("out_", captured.get("out")), ("loss_", captured.get("losses"))):
+        for k, v in (dict.items(d) if d is not None else ()):
+            if isinstance(v, torch.Tensor) and v.is_floating_point():
+                key = "_".join(str(p).replace("-", "m") for p in (k if isinstance(k, tuple) else (k,)))
+                add(prefix + re.sub(r"[^A-Za-z0-9_]", "_", key), v)
+    ps = list(model.parameters())
+    add("params", torch.cat([p.detach().reshape(-1) for p in ps]))
+    add("grads", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in ps]))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -252,7 +304,15 @@ def main():
                          "K = --steps times; prints its own JSON line")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-timeout", type=float, default=150.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel timing + roofline, the reference_step and amp_step "
+                         "blocks, the comm block (N > 1) and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, model outputs, parameters, gradients; "
+                         "large arrays as a fixed seeded sample) to DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_reference_step = args.no_amp_step = True
     if args.cpu_baseline_only:
         Hh, W = WORKLOADS[args.workload][:2]
         print(json.dumps(cpu_baseline(args.workload, Hh, W, args.cpu_baseline_timeout - 25.0)))
@@ -343,6 +403,8 @@ def main():
         unlabeled_inputs["is_labeled"] = (torch.arange(B) % 2 == 0).to(dev)
         del lbl_u
     it = [0]
+    capture = [False]         # --dump-outputs: the step keeps what its caller would receive in `captured`
+    captured = {}
 
     def nosync():
         import contextlib
@@ -368,6 +430,8 @@ def main():
             if "intermediate_semantics" in out:
                 seg = (seg + cross_entropy2d(out["intermediate_semantics"], inputs["lbl"])) / 2
             total = total + seg
+        if capture[0]:
+            captured["out"] = out
         if unlabeled:
             # train.py:511-514: labeled backward, then the unlabeled step accumulates onto the same gradients; only the
             # last backward of the step may start the gradient all-reduce
@@ -414,6 +478,8 @@ def main():
                                unlabeled_inputs=dict(unlabeled_inputs) if unlabeled else None,
                                reducer=reducer if use_reducer[0] else None)
         it[0] += 1
+        if capture[0]:
+            captured["losses"] = out
         return out["total_loss"]
 
     step_summed = step
@@ -549,15 +615,21 @@ def main():
     marks[0].record()
     for i in range(args.steps):
         H.profile_step(i)
+        capture[0] = args.dump_outputs is not None and i == args.steps - 1
         last = step()
         marks[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
     H.PROFILE = None
+    capture[0] = False
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     med_ms = float(np.median(step_ms))
+    if args.dump_outputs is not None and rank == 0:
+        # before anything below runs another step on the same model
+        dump_outputs(args.dump_outputs, last, captured, model)
+    captured.clear()
     comm = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         # why the N-GPU number is what it is, from the same run: how long the collectives occupied their stream per step
         # (event pairs on the reducer's side stream), how much of that the step could NOT hide (this step minus the same step
         # with every backward under no_sync() and no finish(): identical compute, no collective), and every rank's own median

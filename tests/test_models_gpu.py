@@ -377,7 +377,7 @@ def test_bench_selfspawn_two_ranks_one_device():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cp = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "cfg1", "--steps", "2",
-                         "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                         "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert cp.returncode == 0, cp.stderr[-3000:]
     line = cp.stdout.strip().splitlines()[-1]
     res = json.loads(line)
