@@ -849,3 +849,35 @@ class ScaleSliceFn(Function):
     @staticmethod
     def backward(ctx, g):
         return H.axpby(ctx.alpha, g), None
+
+
+class FeatureDistFn(Function):
+    """torch.dist(a, b, p=2) of two NHWC tensors of one shape (train.py:480-483) -> 0-dim device scalar.  Backward: g * (a - b) / d
+    for a and, only if it asks for one, g * (b - a) / d for b (the training step's b, the ImageNet encoder's features, is detached)"""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        d = H.feat_dist_forward(a, b)
+        ctx.save_for_backward(a, b, d)
+        return d
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, d = ctx.saved_tensors
+        g = g.float().contiguous()
+        da = H.feat_dist_backward(a, b, d, g) if ctx.needs_input_grad[0] else None
+        db = H.feat_dist_backward(b, a, d, g) if ctx.needs_input_grad[1] else None
+        return da, db
+
+
+@fp32_region
+def feature_distance(a, b):
+    """torch.dist(a, b, p=2) on the HIP kernels: 4-D operands are NCHW-logical (zero-copy when channels-last in memory, as the
+    package's feature maps are), anything else is taken as a flat vector"""
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("feature_distance of tensors of different shapes: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.dim() == 4:
+        x, y = to_nhwc(a.float()), to_nhwc(b.float())
+    else:
+        x, y = a.float().contiguous().reshape(-1, 1), b.float().contiguous().reshape(-1, 1)
+    return FeatureDistFn.apply(x, y)

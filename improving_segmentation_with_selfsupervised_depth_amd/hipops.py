@@ -1015,6 +1015,32 @@ def colsum(x):
     return out
 
 
+
+def feat_dist_forward(a, b):
+    """||a - b||_2 of two NHWC tensors of one shape (channel slices allowed) -> 0-dim, on the device (torch.dist, train.py:480-483)"""
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("feature distance of tensors of different shapes: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    M, C, lda = _rows(a)
+    ldb = _rows(b)[2]
+    L = _lib.lib()
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    nb = L.segsde_feat_dist_workspace(M, C)
+    ws = _ws(nb, a)
+    _timed('hbm_feat_dist', 8.0 * M * C, a, lambda: check(L.segsde_feat_dist_forward(
+        _p(_f32(a)), lda, _p(_f32(b)), ldb, M, C, _p(out), _p(ws), nb, _stream(a)), "feat_dist_forward"))
+    return out
+
+
+def feat_dist_backward(a, b, dist, grad):
+    """d dist / d a scaled by the upstream gradient ``grad`` (a device scalar) -> dense NHWC like a"""
+    M, C, lda = _rows(a)
+    ldb = _rows(b)[2]
+    L = _lib.lib()
+    da = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+    _timed('hbm_feat_dist_bwd', 12.0 * M * C, a, lambda: check(L.segsde_feat_dist_backward(
+        _p(_f32(a)), lda, _p(_f32(b)), ldb, M, C, _p(_f32(dist)), _p(_f32(grad)), _p(da), C, _stream(a)), "feat_dist_backward"))
+    return da
+
 def maxpool_forward(x):
     B, H, W, C = x.shape
     x = x.contiguous()

@@ -55,3 +55,9 @@ def berhu(input, target, mask, apply_log=False):
     absdiff = torch.abs(target - input) * mask
     C = threshold * torch.max(absdiff).item()
     return torch.mean(torch.where(absdiff <= C, absdiff, (absdiff * absdiff + C * C) / (2 * C)))
+
+
+def feature_distance(a, b):
+    """``torch.dist(outputs["encoder_features"], outputs["imnet_features"], p=2)`` of the feature-distance term (train.py:480-483)
+    on the HIP kernels: deterministic, the result a 0-dim tensor on the device"""
+    return Fn.feature_distance(a, b)

@@ -1,6 +1,12 @@
 """Mirror of models/resnet_encoder.py with its own ResNet-v1.5 (the reference delegates to torchvision 0.7.0:
 BasicBlock / Bottleneck / ResNet._make_layer -- restated here from the published algorithm; module names follow
-torchvision so state_dict keys match: conv1, bn1, layerL.B.convK / bnK / downsample.0 / downsample.1)."""
+torchvision so state_dict keys match: conv1, bn1, layerL.B.convK / bnK / downsample.0 / downsample.1).
+
+``pretrained=True`` reads the ImageNet weights from the file torchvision's model zoo would have cached
+(``torch.hub.get_dir()/checkpoints/<file name>``); nothing is downloaded -- a missing file is a FileNotFoundError."""
+import errno
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -112,13 +118,38 @@ _SPECS = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]), 50: (B
           101: (Bottleneck, [3, 4, 23, 3]), 152: (Bottleneck, [3, 8, 36, 3])}
 
 
+# torchvision 0.7.0's ImageNet checkpoints: the file names torchvision's own loader caches them under
+IMNET_FILES = {18: "resnet18-5c106cde.pth", 34: "resnet34-333f7ec4.pth", 50: "resnet50-19c8e357.pth",
+               101: "resnet101-5d3b4d8f.pth", 152: "resnet152-b121ed2f.pth"}
+
+
+def imnet_checkpoint_path(num_layers):
+    return os.path.join(torch.hub.get_dir(), "checkpoints", IMNET_FILES[num_layers])
+
+
+def load_imnet_weights(resnet, num_layers, num_input_images=1):
+    """torchvision's ``resnetN(pretrained=True)`` / resnet_encoder.py:56-59 on the local file: a strict load (a missing or unexpected
+    key is an error) of everything but the ImageNet classifier ``fc.*`` (models/utils.py:46-47 replaces it by Identity); a stem
+    for ``num_input_images`` frames gets conv1.weight tiled over the frames and divided by their number"""
+    path = imnet_checkpoint_path(num_layers)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(errno.ENOENT, "ImageNet checkpoint not found (nothing is downloaded; place torchvision's file there)",
+                                path)
+    loaded = {k: v for k, v in torch.load(path, map_location="cpu").items() if not k.startswith("fc.")}
+    if num_input_images > 1:
+        loaded["conv1.weight"] = torch.cat([loaded["conv1.weight"]] * num_input_images, 1) / num_input_images
+    resnet.load_state_dict(loaded, strict=True)
+    return resnet
+
+
 def resnet_multiimage_input(num_layers, pretrained=False, num_input_images=1):
     """reference resnet_encoder.py:44-61"""
     assert num_layers in [18, 50], "Can only run with 18 or 50 layer resnet"
-    if pretrained:
-        raise RuntimeError("ImageNet weights need the torchvision model zoo (no network here); load a state_dict instead")
     block, layers = _SPECS[num_layers]
-    return ResNet(block, layers, num_input_images=num_input_images)
+    model = ResNet(block, layers, num_input_images=num_input_images)
+    if pretrained:
+        load_imnet_weights(model, num_layers, num_input_images)
+    return model
 
 
 class ResnetEncoder(nn.Module):
@@ -130,13 +161,13 @@ class ResnetEncoder(nn.Module):
         self.num_ch_enc = np.array([64, 64, 128, 256, 512])
         if num_layers not in _SPECS:
             raise ValueError("{} is not a valid number of resnet layers".format(num_layers))
-        if pretrained:
-            raise RuntimeError("ImageNet weights need the torchvision model zoo (no network here); load a state_dict instead")
         if num_input_images > 1:
             self.encoder = resnet_multiimage_input(num_layers, pretrained, num_input_images)
         else:
             block, layers = _SPECS[num_layers]
             self.encoder = ResNet(block, layers, 1, kwargs.get("replace_stride_with_dilation"))
+            if pretrained:
+                load_imnet_weights(self.encoder, num_layers)
         if num_layers > 34:
             self.num_ch_enc[1:] *= 4
 

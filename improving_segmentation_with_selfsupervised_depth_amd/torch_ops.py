@@ -175,6 +175,12 @@ def depthcomp_mask(depths, margin, fg_threshold):
     return H.depthcomp_mask(depths, float(margin), float(fg_threshold))
 
 
+@_op("feature_distance(Tensor a, Tensor b) -> Tensor")
+def feature_distance(a, b):
+    """torch.dist(a, b, p=2), the feature-distance term of train.py:480-483 (NCHW feature maps; gradients for both operands)"""
+    return Fn.feature_distance(a, b)
+
+
 def names():
     """qualified names of everything registered above"""
     return ["%s::%s" % (NAMESPACE, n) for n in SCHEMAS]

@@ -16,7 +16,7 @@ from .loss.loss import cross_entropy2d
 
 __all__ = ["extract_ema_params", "EmaUpdater", "update_ema_variables", "calc_pseudo_label_loss", "teacher_softmax",
            "normalize_online_depth", "generate_mix_mask", "train_step_segmentation_unlabeled", "create_ema_model", "extract_param_dict",
-           "get_params", "get_train_params", "train_step"]
+           "get_params", "get_train_params", "train_step", "save_monodepth_models"]
 
 
 def extract_ema_params(model, ema_model, model_names):
@@ -307,6 +307,27 @@ def get_train_params(model, cfg):
     return groups
 
 
+def save_monodepth_models(model, cfg, logdir, ema_model=None):
+    """``Trainer.save_monodepth_models`` (train.py:377-390) with the log directory passed in: ``{name}.pth`` = the sub-model's
+    state_dict for depth, pose_encoder, pose and -- unless the backbone is frozen -- encoder; of the EMA model when
+    ``cfg["training"]["save_monodepth_ema"]``.  These are the files models.utils loads for ``mono_*`` pretraining (a directory
+    ``<DOWNLOAD_MODEL_DIR>/<name>/``).  Returns the paths written."""
+    import os
+    if cfg["training"]["save_monodepth_ema"]:
+        assert ema_model is not None
+        model_to_save = ema_model
+    else:
+        model_to_save = model
+    names = ["depth", "pose_encoder", "pose"]
+    if not cfg["model"]["freeze_backbone"]:
+        names.append("encoder")
+    paths = []
+    for name in names:
+        path = os.path.join(logdir, "{}.pth".format(name))
+        torch.save(model_to_save.models[name].state_dict(), path)
+        paths.append(path)
+    return paths
+
 def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calculator, ema_model=None, scheduler=None,
                unlabeled_inputs=None, reducer=None, mIoU=0, scaler=None):
     """``Trainer.train_step`` (train.py:442-549) as a free function over the objects the method reads from ``self``
@@ -320,7 +341,7 @@ def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calc
     ``reducer`` (ddp.GradAllReducer): every backward but the step's last runs under ``no_sync()`` and ``finish()`` is called
     before the clipping."""
     import contextlib
-    from .loss.loss import berhu
+    from .loss.loss import berhu, feature_distance
     tr = cfg["training"]
     amp = bool(tr.get("amp", False))
     if scaler is None:
@@ -371,7 +392,7 @@ def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calc
         monodepth_loss_calculator.generate_images_pred(inputs, outputs)
         mono_loss = tr["monodepth_lambda"] * monodepth_loss_calculator.compute_losses(inputs, outputs)["loss"]
         if tr["feat_dist_lambda"] > 0:
-            feat_dist_loss = tr["feat_dist_lambda"] * torch.dist(outputs["encoder_features"], outputs["imnet_features"], p=2)
+            feat_dist_loss = tr["feat_dist_lambda"] * feature_distance(outputs["encoder_features"], outputs["imnet_features"])
         mono_total = mono_loss + feat_dist_loss
         with hold(not (do_pd or do_seg)):
             scaler.scale(mono_total).backward(retain_graph=True)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 13
+#define SEGSDE_ABI_VERSION 14
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -195,6 +195,17 @@ int segsde_act_backward(const float* dy, int lddy, const float* y, int ldy, long
                         float* dbias, void* workspace, size_t workspace_bytes, void* stream);
 int segsde_colsum(const float* x, int ldx, long M, int C, float* out, void* workspace, size_t workspace_bytes,
                   void* stream);
+
+/* Feature distance of the self-supervised pretraining stage (the dec6 configs' feat_dist_lambda term):
+ * dist[0] = ||a - b||_2 over two fp32 NHWC tensors of M pixels x C channels with pixel pitches lda / ldb -- torch.dist(
+ * outputs["encoder_features"], outputs["imnet_features"], p=2), train.py:480-483.  Deterministic (per-block double partials, a
+ * fixed-order one-block finish, no atomics); the result stays on the device.  workspace: segsde_feat_dist_workspace(M, C) bytes.
+ * Backward: da = grad[0] * (a - b) / dist[0], 0 where dist[0] == 0 (torch's norm backward); b gets no gradient (it is detached). */
+size_t segsde_feat_dist_workspace(long M, int C);
+int segsde_feat_dist_forward(const float* a, int lda, const float* b, int ldb, long M, int C, float* dist, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int segsde_feat_dist_backward(const float* a, int lda, const float* b, int ldb, long M, int C, const float* dist,
+                              const float* grad, float* da, int ldda, void* stream);
 
 /* nn.MaxPool2d(3, 2, 1) (models/resnet_encoder.py:96); idx keeps the winning tap (first max in scan order). */
 int segsde_maxpool3x3s2_forward(const float* x, int B, int H, int W, int C, float* y, uint8_t* idx, void* stream);
