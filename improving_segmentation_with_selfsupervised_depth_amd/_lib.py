@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -38,6 +38,8 @@ class ConvDesc(ctypes.Structure):
 P = c_void_p
 _SIGS = {
     "segsde_abi_version": (c_int, []),
+    "segsde_conv_compute_taken": (c_int, [POINTER(ConvDesc), c_int]),
+    "segsde_split_bf16_planes": (c_int, [P, c_long, P, P, P, P]),
     "segsde_conv2d_forward": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P]),
     "segsde_conv2d_stats_rows": (c_long, [POINTER(ConvDesc)]),
     "segsde_conv2d_forward_stats": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P]),

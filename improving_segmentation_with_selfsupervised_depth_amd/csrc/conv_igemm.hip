@@ -77,7 +77,7 @@ struct ConvP {
   // whose first row lies in image b of the B-image input reads its weight rows from w + b * wbstride floats.  0: one weight.
   long wbstride;
   int nt;       // 1: the staged epilogue's full-tile stores are streaming stores (set by the launcher for outputs beyond the caches)
-  int f16;      // 1: half-precision operands on the LDS-DMA loop (segsde_conv_desc.compute)
+  int cmp;      // operand arithmetic asked of the LDS-DMA loops (segsde_conv_desc.compute): 1 fp16, 2 split bf16 (nine products)
 };
 constexpr int SEGSDE_PAD_CLAMP_ = 3;   // internal (never crosses the ABI)
 
@@ -260,17 +260,21 @@ __device__ __forceinline__ float4 fast_fetch(const ConvP& p, const SrcSel& s, in
 // VAR: experiment variants of the LDS-DMA loop (SEGSDE_TUNE="var=N"; 0 = shipped): 1 = all tile loads of a chunk issued
 // up front, 2 = no scheduling fences between the MFMA units, 3 = raised wave priority around the MFMA units, 4 = (with BK = 16)
 // four LDS stages: the loads of chunk k+3 are issued during chunk k, two chunks of loads stay in flight across barriers
-// VARX >= 16 (MODE 4 only): HALF-PRECISION OPERANDS, the arithmetic of the reference's `amp: True` mode (torch autocast runs its
+// VARX = VAR + 16 * CMP (MODE 4 only), CMP = segsde_conv_desc.compute of the instantiation.  CMP 1: HALF-PRECISION OPERANDS, the arithmetic of the reference's `amp: True` mode (torch autocast runs its
 // convolutions on fp16 inputs with fp32 accumulation).  Tiles still travel as fp32 (LDS-DMA cannot convert); a lane's two
 // fragment reads of a 16-deep k block (4 + 4 consecutive floats per operand row) are rounded to eight halves
 // (v_cvt_pk_f16_f32, round to nearest even) and ONE v_mfma_f32_32x32x16_f16 replaces eight v_mfma_f32_32x32x2_f32 -- which k
 // sits in which of the instruction's sixteen slots does not matter as long as both operands agree, and they do (same read
 // pattern).  Accumulators, epilogues, statistics: unchanged fp32.
+// CMP 2: SPLIT-BF16 OPERANDS.  The same two fragment reads per operand row, each of the eight fp32 values split into three bf16
+// numbers that sum to it exactly (segsde_split_bf16, segsde_common.h: also what becomes of non-finite and tiny operands), and
+// NINE v_mfma_f32_32x32x16_bf16 per accumulator and k block, smallest products first -- fp32 re-associated, not reduced precision.
 template <int BM, int BN, int WM, int WN, int MODE, int BK, int VARX = 0>
 __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kernel(ConvP p) {
   constexpr int VAR = VARX & 15;
-  constexpr bool F16 = VARX >= 16;
-  static_assert(!F16 || MODE == 4, "half-precision operands: LDS-DMA loop only");
+  constexpr int CMP = VARX >> 4;            // segsde_conv_desc.compute of this instantiation
+  constexpr bool F16 = CMP == 1, SPLIT = CMP == 2;
+  static_assert(CMP <= 2 && (CMP == 0 || MODE == 4), "half-precision / split-bf16 operands: LDS-DMA loop only");
   constexpr bool VEC = MODE >= 1;
   constexpr bool FAST = MODE >= 2;
   constexpr bool ADJ = MODE == 3;
@@ -733,6 +737,22 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
                   for (int j = 0; j < TN; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ha[i], hb[j], (FIRST && u == 4) ? f32x16{} : acc[i][j], 0, 0, 0);
               }
+            } else if constexpr (SPLIT) {
+              // the same 16-deep k block, each operand row split into three bf16 operands (segsde_split_bf16): nine products per
+              // accumulator, smallest first
+              if ((g & 1) == 1 && st == 0) {
+                bf16x8 ah[TM], am[TM], al[TM], bh[TN], bm[TN], bl[TN];
+  #pragma unroll
+                for (int i = 0; i < TM; ++i) segsde_split_bf16(fa[0][i], fa[1][i], ah[i], am[i], al[i]);
+  #pragma unroll
+                for (int j = 0; j < TN; ++j) segsde_split_bf16(fb[0][j], fb[1][j], bh[j], bm[j], bl[j]);
+  #pragma unroll
+                for (int i = 0; i < TM; ++i)
+  #pragma unroll
+                  for (int j = 0; j < TN; ++j)
+                    acc[i][j] = segsde_mfma_split(ah[i], am[i], al[i], bh[j], bm[j], bl[j],
+                                                            (FIRST && u == 4) ? f32x16{} : acc[i][j]);
+              }
             } else {
   #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -1164,15 +1184,17 @@ constexpr int BP = 32;  // pixels per staged chunk
 // ~14 us stay.  tickets == nullptr (default): partial slabs only, a separate reduce kernel follows.
 struct WRed { unsigned* tickets; float* dw; int CtotDst, cOff, taps, srcC0; };
 
-// MODEX >= 16 (with MODE 5): half-precision operands, like conv_igemm_kernel's VARX >= 16 -- the eight scalars a lane reads for
+// MODEX = MODE + 16 * CMP (with MODE 5), CMP as in conv_igemm_kernel.  CMP 1: half-precision operands -- the eight scalars a lane reads for
 // eight consecutive fp32 MFMAs of a 16-pixel block (pixels 2 u + lane half of two fragment groups) become ONE operand of
-// v_mfma_f32_32x32x16_f16; both operands are read with the same pattern, so the k slots agree
+// v_mfma_f32_32x32x16_f16; both operands are read with the same pattern, so the k slots agree.  CMP 2: split-bf16 operands, the
+// same eight scalars split into three bf16 operands each, nine v_mfma_f32_32x32x16_bf16 per accumulator
 template <int BKT, int BN, int WM, int WN, int MODEX>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float* dy, int lddy, float* part,
                                                          int chunks_per_split, WRed wr) {
   constexpr int MODE = MODEX & 15;
-  constexpr bool F16 = MODEX >= 16;
-  static_assert(!F16 || MODE == 5, "half-precision operands: the pipelined LDS-DMA loop only");
+  constexpr int CMP = MODEX >> 4;           // segsde_conv_desc.compute of this instantiation
+  constexpr bool F16 = CMP == 1, SPLIT = CMP == 2;
+  static_assert(CMP <= 2 && (CMP == 0 || MODE == 5), "half-precision / split-bf16 operands: the pipelined LDS-DMA loop only");
   // MODE 0: scalar gather, 1: float4 gather, 2: FAST A side + vector dY + rows at least 32 pixels wide (straight-line
   // loop), 3: FAST A side with the general row walk / scalar dY (odd Cout, tiny feature maps), 4: MODE 2 with the tile
   // loads writing LDS themselves (LDS-DMA, see the forward kernel), 5: MODE 4 with the chunk's barrier moved into the chunk
@@ -1595,6 +1617,23 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
               }
             }
           }
+        } else if constexpr (SPLIT) {
+          if ((g & 1) == 1 && st == 0) {           // the same sixteen pixels, operands split into three bf16 each
+            bf16x8 ah[TM], am[TM], al[TM], dh[TN], dm[TN], dl[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+              segsde_split_bf16(make_float4(fa[0][0][i], fa[0][1][i], fa[0][2][i], fa[0][3][i]),
+                                make_float4(fa[1][0][i], fa[1][1][i], fa[1][2][i], fa[1][3][i]), ah[i], am[i], al[i]);
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              segsde_split_bf16(make_float4(fd[0][0][j], fd[0][1][j], fd[0][2][j], fd[0][3][j]),
+                                make_float4(fd[1][0][j], fd[1][1][j], fd[1][2][j], fd[1][3][j]), dh[j], dm[j], dl[j]);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int j = 0; j < TN; ++j)
+                acc[i][j] = segsde_mfma_split(ah[i], am[i], al[i], dh[j], dm[j], dl[j], acc[i][j]);
+          }
         } else {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -1853,6 +1892,18 @@ const Tune& tune() {
   return t;
 }
 
+// segsde_conv_compute_taken runs the entry points' own dispatch with this set: every implicit-GEMM launch reports the arithmetic
+// it would run in (launch_igemm / launch_wgrad, from the predicates they dispatch on) and nothing is launched
+struct ComputeProbe { int launches = 0, lo = 3, hi = 0; };
+thread_local ComputeProbe* g_probe = nullptr;
+inline bool probing() { return g_probe != nullptr; }
+inline int probe_note(int cmp) {
+  ++g_probe->launches;
+  if (cmp < g_probe->lo) g_probe->lo = cmp;
+  if (cmp > g_probe->hi) g_probe->hi = cmp;
+  return 0;
+}
+
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 const float* zero_page() {
@@ -1909,7 +1960,7 @@ ConvP make_params(const segsde_conv_desc* d, const float* x0, const float* x1, c
     if (nt_bytes < 0) { const char* e = getenv("SEGSDE_CONV_NT_MB"); nt_bytes = (e ? atol(e) : 0L) << 20; }
     p.nt = (nt_bytes > 0 && (long)p.M * p.N * 4 >= nt_bytes) ? 1 : 0;
   }
-  p.f16 = d->compute == 1 ? 1 : 0;
+  p.cmp = (d->compute == 1 || d->compute == 2) ? d->compute : 0;
   p.agy = nullptr; p.agld = 0; p.agkind = 0;
   p.lin = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->in_div <= 1 && !d->up0 && !d->sum2x2 && d->C1 == 0 &&
           d->H == d->Ho && d->W == d->Wo;
@@ -1936,6 +1987,10 @@ int validate(const segsde_conv_desc* d) {
        d->H != d->Ho || d->W != d->Wo || d->H < 2 || d->W < 2))
     return SEGSDE_ERR_SHAPE;
   if (d->ld0 < d->C0 || (d->C1 && d->ld1 < d->C1) || d->ldy <= 0) return SEGSDE_ERR_SHAPE;
+  // compute = 3, the six-product split (m.l, l.m, l.l dropped; 192 instead of 288 matrix cycles per k block): built and measured --
+  // 0.96-1.34x the fp32 launches, but its maximum error on the 1x1 1024 -> 256 forward was 1.66x the fp32 kernel's against a gate
+  // of 1.5x (profiles/split_bf16_layers.md) -- so it is not shipped
+  if (d->compute == 3) return SEGSDE_ERR_UNSUPPORTED;
   return 0;
 }
 
@@ -1968,14 +2023,35 @@ int launch_igemm_mode(const ConvP& p, hipStream_t stream) {
   return 0;
 }
 
+// The arithmetic launch_igemm<.., BN, ..> runs p in: p.cmp where the launch takes the shipped LDS-DMA loop (MODE 4), else 0 -- the
+// in-kernel reflection adjoint (MODE 3), the experiment variants of SEGSDE_TUNE and the gathers have fp32 instantiations only.
+// launch_igemm dispatches on this value and segsde_conv_compute_taken reports it.
+template <int BN>
+int igemm_compute(const ConvP& p) {
+  if (!p.cmp || !igemm_fast_ok(p)) return 0;
+  if (p.pad_mode == SEGSDE_PAD_CLAMP_) return p.cmp;
+  if (p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && !(tune().adjfix && !p.sum2x2) && tune().adjfix < 2) return 0;
+  if ((tune().bk64 && bk64_ok(p)) || !tune().dma) return 0;
+  const int v = tune().var;
+  if (v == 1 || v == 2 || v == 3 || v == 7 || (v == 4 && BN >= 64) || (v == 6 && BN == 64)) return 0;
+  return p.cmp;
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_igemm(const ConvP& p, hipStream_t stream) {
+  const int cmp = igemm_compute<BN>(p);
+  if (probing()) return probe_note(cmp);
+  if (cmp) {
+    if (p.pad_mode == SEGSDE_PAD_CLAMP_)   // upsample-folded class launches
+      return cmp == 1 ? launch_igemm_mode<BM, BN, WM, WN, 4, 32, 16 + 9>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 4, 32, 32 + 9>(p, stream);
+    return cmp == 1 ? launch_igemm_mode<BM, BN, WM, WN, 4, 32, 16>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 4, 32, 32>(p, stream);
+  }
   if (igemm_fast_ok(p) && p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && !(tune().adjfix && !p.sum2x2) && tune().adjfix < 2)
     return tune().var == 8 ? launch_igemm_mode<BM, BN, WM, WN, 3, 32, 8>(p, stream)
            : (tune().adjlds ? launch_igemm_mode<BM, BN, WM, WN, 3, 32>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 3, 32, 5>(p, stream));
   if (p.pad_mode == SEGSDE_PAD_CLAMP_) { // upsample-folded class launches (host guarantees the FAST conditions)
     if (!igemm_fast_ok(p)) return SEGSDE_ERR_UNSUPPORTED;
-    return p.f16 ? launch_igemm_mode<BM, BN, WM, WN, 4, 32, 16 + 9>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 4, 32, 9>(p, stream);
+    return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 9>(p, stream);
   }
   if (tune().bk64 && bk64_ok(p)) return launch_igemm_mode<BM, BN, WM, WN, 2, 64>(p, stream);
   if (igemm_fast_ok(p) && tune().dma) {
@@ -1989,7 +2065,6 @@ int launch_igemm(const ConvP& p, hipStream_t stream) {
     if constexpr (BN == 64) {
       if (tune().var == 6) return launch_igemm_mode<BM, BN, WM, WN, 4, 16, 6>(p, stream);
     }
-    if (p.f16) return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 16>(p, stream);
     return launch_igemm_mode<BM, BN, WM, WN, 4, 32>(p, stream);
   }
   if (igemm_fast_ok(p)) return launch_igemm_mode<BM, BN, WM, WN, 2, 32>(p, stream);
@@ -1999,6 +2074,7 @@ int launch_igemm(const ConvP& p, hipStream_t stream) {
 
 int launch_reflect_fix(const float* dy, int lddy, const float* wd, float* dx, int lddx, float* dx2, int lddx2, int nsplit,
                        int B, int H, int W, int Cin, int Cout, hipStream_t s) {
+  if (probing()) return 0;
   if (!dx2) { dx2 = dx; lddx2 = lddx; nsplit = Cin; }
   const long total = (long)B * (2 * W + 2 * H) * Cin;
   hipLaunchKernelGGL(reflect_dgrad_fix_kernel, dim3(min(4096, segsde_cdiv(total, 256))), dim3(256), 0, s, dy, lddy, wd, dx,
@@ -2108,6 +2184,7 @@ int launch_adjoint_by_borders(const ConvP& p, hipStream_t s, bool with_main = tr
     if (int e = launch_by_n(q, s)) return e;
   for (int k = 0; k < 4; ++k)
     if (int e = launch_by_n(bl[k], s)) return e;
+  if (probing()) return 0;
   hipLaunchKernelGGL(adjoint_corner_kernel, dim3(segsde_cdiv((long)p.B * 4 * p.N, 256)), dim3(256), 0, s, p.x0, p.ld0, p.w, p.y, p.ldy,
                      p.y2, p.ldy2, p.nsplit, p.B, p.H, p.W, p.N, p.Ctot, p.agy, p.agld, p.agkind, 0);
   SEGSDE_CHECK_LAUNCH();
@@ -2116,8 +2193,8 @@ int launch_adjoint_by_borders(const ConvP& p, hipStream_t s, bool with_main = tr
 bool adjoint_by_borders_ok(const ConvP& p) {
   // measured (profiles/experiments_r03.md): the five extra launches cost ~70 us per call -- a gain only on the largest maps
   // (128 -> 64 @256x512 x 16: 5.63 -> 5.46 ms/step), a loss below (256 -> 256 @32x64: 0.69 -> 1.15); adjb=2 forces it everywhere
-  // (half-precision operand mode: always -- the in-kernel adjoint, MODE 3, has no half-precision variant and would run in fp32)
-  const bool big = (long)p.B * p.H * p.W >= (1L << 21) || tune().adjb == 2 || p.f16;
+  // (half-precision / split-bf16 operand modes: always -- the in-kernel adjoint, MODE 3, has fp32 instantiations only)
+  const bool big = (long)p.B * p.H * p.W >= (1L << 21) || tune().adjb == 2 || p.cmp;
   return tune().adjb && big && p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && igemm_fast_ok(p) && !p.sum2x2 && p.vecout && p.H >= 4 &&
          p.W >= 4 && p.C1 == 0 && p.KH == 3 && p.KW == 3 && p.nb == 0 && p.ne == p.N;
 }
@@ -2210,18 +2287,18 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
                         d->in_div <= 1 && !d->sum2x2 && d->H == d->Ho && d->W == d->Wo;
   if (plain3x3 && d->Cout == 1 && d->pad_mode != SEGSDE_PAD_REFLECT_ADJOINT && segsde_c1_supported(d->C0, d->ld0) &&
       aligned16(x0) && aligned16(wpack))
-    return segsde_c1_forward(x0, d->ld0, d->B, d->H, d->W, d->C0, wpack, bias, d->pad_mode == SEGSDE_PAD_REFLECT, d->act, y,
+    return probing() ? 0 : segsde_c1_forward(x0, d->ld0, d->B, d->H, d->W, d->C0, wpack, bias, d->pad_mode == SEGSDE_PAD_REFLECT, d->act, y,
                              d->ldy, stream);
   if (plain3x3 && d->C0 == 1 && d->pad_mode != SEGSDE_PAD_REFLECT && !bias && d->act == 0 &&
       segsde_c1_supported(d->Cout, p.ldy) && p.vecout)
-    return segsde_c1_dgrad(x0, d->ld0, d->B, d->H, d->W, d->Cout, wpack, d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT, y, p.ldy,
+    return probing() ? 0 : segsde_c1_dgrad(x0, d->ld0, d->B, d->H, d->W, d->Cout, wpack, d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT, y, p.ldy,
                            y2, p.ldy2, p.nsplit, p.agy, p.agld, p.agkind, stream);
   // 1x1 with a narrow, non-vectorisable input side (data-gradient of the 19-class head): HBM-bound register kernel
   const bool plain1x1 = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->C1 == 0 && !d->up0 && d->in_div <= 1 &&
                         !d->sum2x2 && d->H == d->Ho && d->W == d->Wo;
   if (plain1x1 && !stats && !p.agy && d->C0 % 4 != 0 && d->ld0 == d->C0 && aligned16(x0) && !bias && d->act == 0 && !y2 &&
       segsde_skinny_supported(d->C0, d->Cout) && p.vecout)
-    return segsde_skinny_nk(x0, d->C0, wpack, (long)d->B * d->H * d->W, d->Cout, y, p.ldy, stream);
+    return probing() ? 0 : segsde_skinny_nk(x0, d->C0, wpack, (long)d->B * d->H * d->W, d->Cout, y, p.ldy, stream);
   // Data-gradient of a stride-2 convolution (in_div == 2): three quarters of the (pixel, tap) pairs hit the holes between
   // the strided outputs.  Split the gradient image into its four (row parity, column parity) classes: each class is a
   // dense stride-1 problem over the taps of matching parity (1 / 2 / 2 / 4 of the 9 taps of a 3x3, 1 / 0 / 0 / 0 of a 1x1)
@@ -2254,7 +2331,7 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
       }
     if (!ok && d->accumulate) return SEGSDE_ERR_UNSUPPORTED;
     if (ok) {
-      if (empty && !d->accumulate) {   // 1x1: only the (even, even) class receives anything (accumulating: the rest keeps what it holds)
+      if (empty && !d->accumulate && !probing()) {   // 1x1: only the (even, even) class receives anything (accumulating: the rest keeps what it holds)
         if (hipMemsetAsync(y, 0, (size_t)d->B * d->Ho * d->Wo * p.ldy * sizeof(float), s) != hipSuccess) return SEGSDE_ERR_SHAPE;
       }
       for (int i = 0; i < nsub; ++i) {
@@ -2316,12 +2393,22 @@ int wgrad_mode(const ConvP& p, const float* dy, int lddy) {
   return vec ? 1 : 0;
 }
 
+// The arithmetic launch_wgrad runs p in: p.cmp on the pipelined LDS-DMA loop (MODE 5), else 0 (the other loops are fp32 only).
+// launch_wgrad dispatches on this value and segsde_conv_compute_taken reports it.
+int wgrad_compute(const ConvP& p, const float* dy, int lddy) {
+  return (p.cmp && wgrad_mode(p, dy, lddy) == 2 && tune().wdma == 2) ? p.cmp : 0;
+}
+
 template <int BKT, int BN, int WM, int WN>
 int launch_wgrad(const ConvP& p, const float* dy, int lddy, float* ws, int splits, int cps, hipStream_t stream, WRed wr = WRed{}) {
+  const int cmp = wgrad_compute(p, dy, lddy);
+  if (probing()) return probe_note(cmp);
+  if (cmp)
+    return cmp == 1 ? launch_wgrad_mode<BKT, BN, WM, WN, 16 + 5>(p, dy, lddy, ws, splits, cps, stream, wr)
+                    : launch_wgrad_mode<BKT, BN, WM, WN, 32 + 5>(p, dy, lddy, ws, splits, cps, stream, wr);
   switch (wgrad_mode(p, dy, lddy)) {
     case 2:
-      if (tune().wdma == 2) return p.f16 ? launch_wgrad_mode<BKT, BN, WM, WN, 16 + 5>(p, dy, lddy, ws, splits, cps, stream, wr)
-                                         : launch_wgrad_mode<BKT, BN, WM, WN, 5>(p, dy, lddy, ws, splits, cps, stream, wr);
+      if (tune().wdma == 2) return launch_wgrad_mode<BKT, BN, WM, WN, 5>(p, dy, lddy, ws, splits, cps, stream, wr);
       if (tune().wdma) return launch_wgrad_mode<BKT, BN, WM, WN, 4>(p, dy, lddy, ws, splits, cps, stream, wr);
       return launch_wgrad_mode<BKT, BN, WM, WN, 2>(p, dy, lddy, ws, splits, cps, stream, wr);
     case 3: return launch_wgrad_mode<BKT, BN, WM, WN, 3>(p, dy, lddy, ws, splits, cps, stream, wr);
@@ -2332,7 +2419,7 @@ int launch_wgrad(const ConvP& p, const float* dy, int lddy, float* ws, int split
 
 WRed make_wred(const ConvP& p, int bkt, int bn, float* dw, int CtotDst, int cOff, int taps, int srcC0) {
   WRed wr{};
-  if (!tune().wred) return wr;
+  if (!tune().wred || probing()) return wr;
   wr.tickets = segsde_ticket_slice(segsde_cdiv(p.Ktot, bkt) * segsde_cdiv(p.N, bn));
   wr.dw = dw; wr.CtotDst = CtotDst; wr.cOff = cOff; wr.taps = taps; wr.srcC0 = srcC0;
   return wr;
@@ -2394,7 +2481,7 @@ extern "C" int segsde_conv2d_wgrad(const segsde_conv_desc* d, const float* x0, c
   if (!x0 || !dy || !dw_oihw || !workspace || (d->C1 && !x1)) return SEGSDE_ERR_NULL;
   if (workspace_bytes < segsde_conv2d_wgrad_workspace(d)) return SEGSDE_ERR_WORKSPACE;
   if (c1_wgrad_route(d) && aligned16(x0))
-    return segsde_c1_wgrad(x0, d->ld0, d->B, d->H, d->W, d->C0, dy, lddy, d->pad_mode == SEGSDE_PAD_REFLECT, dw_oihw, workspace,
+    return probing() ? 0 : segsde_c1_wgrad(x0, d->ld0, d->B, d->H, d->W, d->C0, dy, lddy, d->pad_mode == SEGSDE_PAD_REFLECT, dw_oihw, workspace,
                            stream);
   ConvP p = make_params(d, x0, x1, dy /*unused as w; keeps alignment test meaningful*/, nullptr, workspace, nullptr);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2407,7 +2494,7 @@ extern "C" int segsde_conv2d_wgrad(const segsde_conv_desc* d, const float* x0, c
   else if (bn == 64) e = launch_wgrad<128, 64, 2, 2>(p, dy, lddy, workspace, splits, cps, s, wr);
   else e = launch_wgrad<128, 128, 2, 2>(p, dy, lddy, workspace, splits, cps, s, wr);
   if (e) return e;
-  if (wr.tickets) return 0;
+  if (wr.tickets || probing()) return 0;
   const long total = (long)p.Ktot * p.N;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, workspace, splits,
                      p.Ktot, p.N, p.Ctot, d->KH * d->KW, (wgrad_mode(p, dy, lddy) == 2 && p.C1 > 0) ? p.C0 : 0, dw_oihw, p.Ctot, 0);
@@ -2683,11 +2770,13 @@ extern "C" int segsde_conv2d_dgrad_upfold(const segsde_conv_desc* d, const float
     if (ok) {
       for (int k = 0; k < 4; ++k)
         if (int e = launch_by_n(bl[k], s)) return e;
+      if (!probing())
       hipLaunchKernelGGL(upfold_dgrad_corner_kernel, dim3(segsde_cdiv((long)d->B * 4 * d->C0, 256)), dim3(256), 0, s, dy, lddy, wdfold,
                          dx0, d->C0, d->B, H2, W2, d->C0, d->Cout, act_out, act_ld, act_kind);
       SEGSDE_CHECK_LAUNCH();
     } else {
       const long total = (long)d->B * (2 * W2 + 2 * H2) * d->C0;
+      if (!probing())
       hipLaunchKernelGGL(upfold_dgrad_fix_kernel, dim3(min(8192, segsde_cdiv(total, 256))), dim3(256), 0, s, dy, lddy, wfold, dx0,
                          d->C0, d->B, H2, W2, d->C0, d->Cout, act_out, act_ld, act_kind);
       SEGSDE_CHECK_LAUNCH();
@@ -2761,7 +2850,7 @@ extern "C" int segsde_conv2d_wgrad_upfold(const segsde_conv_desc* d, const float
   }
   for (int k = 0; k < 4; ++k)
     if (int e = launch_wgrad_by_bn(pl.bn, cls[k], dy, lddy, workspace + k * slab, pl.splits, pl.cps, s, WRed{})) return e;
-  {
+  if (!probing()) {
     const long total = (long)d->Cout * d->C0 * 9;
     hipLaunchKernelGGL(upfold_wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, workspace, pl.splits,
                        d->C0, d->Cout, dw_oihw, Ctot);
@@ -2771,13 +2860,75 @@ extern "C" int segsde_conv2d_wgrad_upfold(const segsde_conv_desc* d, const float
     float* ws1 = workspace + 4 * slab;
     const WRed wr = make_wred(r, 128, pl.bn1, dw_oihw, Ctot, d->C0, 9, 0);
     if (int e = launch_wgrad_by_bn(pl.bn1, r, dy, lddy, ws1, pl.splits1, pl.cps1, s, wr)) return e;
-    if (wr.tickets) return 0;
+    if (wr.tickets || probing()) return 0;
     const long total = (long)r.Ktot * r.N;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, ws1, pl.splits1, r.Ktot, r.N, r.Ctot, 9, 0,
                        dw_oihw, Ctot, d->C0);
     SEGSDE_CHECK_LAUNCH();
   }
   return 0;
+}
+
+// segsde_split_bf16 (segsde_common.h) on an array: what the split-bf16 loops make of their operands, for tests and probes
+namespace {
+__global__ __launch_bounds__(256) void split_bf16_kernel(const float* x, long n, unsigned short* h, unsigned short* m, unsigned short* l) {
+  typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+  for (long g = blockIdx.x * 256L + threadIdx.x; g * 8 < n; g += (long)gridDim.x * 256) {
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = g * 8 + q < n ? x[g * 8 + q] : 0.f;
+    bf16x8 bh, bm, bl;
+    segsde_split_bf16(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), bh, bm, bl);
+    const u16x8 uh = __builtin_bit_cast(u16x8, bh), um = __builtin_bit_cast(u16x8, bm), ul = __builtin_bit_cast(u16x8, bl);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (g * 8 + q < n) { h[g * 8 + q] = uh[q]; m[g * 8 + q] = um[q]; l[g * 8 + q] = ul[q]; }
+  }
+}
+}  // namespace
+
+extern "C" int segsde_split_bf16_planes(const float* x, long n, unsigned short* h, unsigned short* m, unsigned short* l, void* stream) {
+  if (!x || !h || !m || !l) return SEGSDE_ERR_NULL;
+  if (n <= 0) return SEGSDE_ERR_SHAPE;
+  hipLaunchKernelGGL(split_bf16_kernel, dim3(min(2048, segsde_cdiv(segsde_cdiv(n, 8), 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     x, n, h, m, l);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The operand arithmetic (0 fp32, 1 fp16, 2 split bf16) the launchers WILL use for d: the entry point of that direction runs
+// its own dispatch on stand-in pointers (16-byte aligned, dense rows) with the launches replaced by a note of what each
+// implicit-GEMM launch would run in.  d->compute is returned when every such launch of the call takes it, 0 when any of them (or
+// the whole call: HBM-bound stencil routes, rejected shapes) computes in fp32.  Host only; nothing is launched.
+extern "C" int segsde_conv_compute_taken(const segsde_conv_desc* d, int direction) {
+  if (!d || validate(d)) return 0;
+  float* fake = reinterpret_cast<float*>(16);
+  const float* x1 = d->C1 ? fake : nullptr;
+  ComputeProbe pr;
+  g_probe = &pr;
+  int e;
+  switch (direction) {
+    case SEGSDE_DIR_FORWARD:
+    case SEGSDE_DIR_DGRAD:
+      e = segsde_conv2d_dgrad_actgrad(d, fake, x1, fake, nullptr, fake, d->ldy2 ? fake : nullptr, nullptr, nullptr, 0, 0, nullptr);
+      break;
+    case SEGSDE_DIR_WGRAD:
+      e = segsde_conv2d_wgrad(d, fake, x1, fake, d->Cout, fake, fake, segsde_conv2d_wgrad_workspace(d), nullptr);
+      break;
+    case SEGSDE_DIR_FORWARD | SEGSDE_DIR_UPFOLD:
+      e = segsde_conv2d_forward_upfold(d, fake, x1, fake, fake, nullptr, fake, nullptr);
+      break;
+    case SEGSDE_DIR_DGRAD | SEGSDE_DIR_UPFOLD:
+      e = segsde_conv2d_dgrad_upfold(d, fake, d->Cout, fake, fake, fake, fake, d->C1 ? fake : nullptr, 0, nullptr, 0, 0, nullptr);
+      break;
+    case SEGSDE_DIR_WGRAD | SEGSDE_DIR_UPFOLD:
+      e = segsde_conv2d_wgrad_upfold(d, fake, x1, fake, d->Cout, fake, fake, segsde_conv2d_wgrad_upfold_workspace(d), nullptr);
+      break;
+    default: e = SEGSDE_ERR_UNSUPPORTED;
+  }
+  g_probe = nullptr;
+  if (e || pr.launches == 0 || pr.lo != pr.hi) return 0;
+  return pr.lo;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -20,6 +20,85 @@ __device__ __forceinline__ f16x8 segsde_pack_f16(const float4& a, const float4& 
   return r;
 }
 
+// Split-bf16 operands (segsde_conv_desc.compute = 2, conv_igemm.hip): an fp32 number is EXACTLY the sum of three bf16
+// numbers  h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)  (round to nearest even; both subtractions are exact in fp32: h
+// keeps the leading 8 significand bits, x - h the next 16 at most, x - h - m the last 8), and a product of two bf16 numbers is
+// exact in fp32 -- so a . b is nine bf16 x bf16 products accumulated in fp32 by v_mfma_f32_32x32x16_bf16, fp32 re-associated
+// rather than reduced precision.  The residual lines must not be contracted or re-associated (the sources are compiled with
+// -ffp-contract=off; the pragma below says it again where it matters).
+// Non-finite operands: x = +-inf gives h = +-inf, x - h = NaN, so m = l = NaN and every result the operand feeds is NaN; x = NaN
+// gives NaN; a finite |x| >= 2^128 - 2^119 rounds to h = inf and ends as NaN too.  Non-finite in => non-finite out, which is all
+// an overflow check (GradScaler) needs.  Tiny operands: bf16 has fp32's exponent range but 8 significand bits, so the residuals
+// of |x| < 2^-108 fall (partly) below the smallest bf16 subnormal 2^-133 and their low terms are lost (the result is then x
+// rounded to fewer bits, never garbage).
+// The kernels call segsde_mfma_bf16 / segsde_split_bf16, never the raw builtins: compiled for the host (the CPU interpreter
+// under tests/ compiles these sources as plain C++, __HIP__ undefined) the conversion is an explicit round-to-nearest-even on the
+// bit pattern and the instruction is eight 2-deep fp32 MFMA steps on the widened operands -- element q of the two lane halves
+// is one step; bf16 x bf16 products are exact in fp32, so that is the instruction's arithmetic up to the summation order.
+#ifdef __HIP__
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 segsde_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x16 segsde_mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+// two floats -> two bf16 (v_cvt_pk_bf16_f32: round to nearest even), and the two bf16 widened back (one shift, one mask)
+__device__ __forceinline__ unsigned segsde_cvt_pk_bf16(float a, float b) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, segsde_bf16x2));
+}
+#else
+typedef unsigned short bf16x8 __attribute__((ext_vector_type(8)));
+inline unsigned segsde_bf16_rne_bits(float x) {
+  unsigned u;
+  __builtin_memcpy(&u, &x, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;      // NaN stays NaN (quiet)
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                       // ties to even; overflow carries into the exponent: inf
+}
+inline unsigned segsde_cvt_pk_bf16(float a, float b) { return segsde_bf16_rne_bits(a) | (segsde_bf16_rne_bits(b) << 16); }
+inline f32x16 segsde_mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
+  f32x16 t = {};      // the sixteen products are summed first, then added to c (one rounding against the running sum per instruction)
+  for (int q = 0; q < 8; ++q) {
+    const unsigned ua = (unsigned)a[q] << 16, ub = (unsigned)b[q] << 16;
+    float fa, fb;
+    __builtin_memcpy(&fa, &ua, 4);
+    __builtin_memcpy(&fb, &ub, 4);
+    t = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, t, 0, 0, 0);
+  }
+  return c + t;
+}
+#endif
+// the eight fp32 values a lane holds for one 16-deep k block (the two float4 fragment reads of segsde_pack_f16: both operands
+// use the same slots) -> three bf16x8 operands with h + m + l == x element by element
+__device__ __forceinline__ void segsde_split_bf16(const float4& a, const float4& b, bf16x8& h, bf16x8& m, bf16x8& l) {
+#pragma clang fp contract(off)
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  u32x4_t ph, pm, pl;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float x0 = x[2 * q], x1 = x[2 * q + 1];
+    const unsigned hh = segsde_cvt_pk_bf16(x0, x1);
+    const float r0 = x0 - __uint_as_float(hh << 16), r1 = x1 - __uint_as_float(hh & 0xffff0000u);      // exact
+    const unsigned mm = segsde_cvt_pk_bf16(r0, r1);
+    const float s0 = r0 - __uint_as_float(mm << 16), s1 = r1 - __uint_as_float(mm & 0xffff0000u);      // exact
+    ph[q] = hh; pm[q] = mm; pl[q] = segsde_cvt_pk_bf16(s0, s1);
+  }
+  h = __builtin_bit_cast(bf16x8, ph); m = __builtin_bit_cast(bf16x8, pm); l = __builtin_bit_cast(bf16x8, pl);
+}
+// the nine products of one 16-deep k block, smallest first into the one fp32 accumulator
+__device__ __forceinline__ f32x16 segsde_mfma_split(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
+                                                    const bf16x8& bm, const bf16x8& bl, f32x16 c) {
+  c = segsde_mfma_bf16(al, bl, c);
+  c = segsde_mfma_bf16(am, bl, c);
+  c = segsde_mfma_bf16(al, bm, c);
+  c = segsde_mfma_bf16(am, bm, c);
+  c = segsde_mfma_bf16(ah, bl, c);
+  c = segsde_mfma_bf16(al, bh, c);
+  c = segsde_mfma_bf16(ah, bm, c);
+  c = segsde_mfma_bf16(am, bh, c);
+  return segsde_mfma_bf16(ah, bh, c);
+}
+
 // all LDS lives in the dynamic region (16-byte aligned base, cdna_hip_programming.md G17)
 #ifndef SEGSDE_SMEM
 #define SEGSDE_SMEM extern __shared__ __attribute__((aligned(16))) unsigned char segsde_smem[]

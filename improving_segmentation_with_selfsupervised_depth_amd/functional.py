@@ -70,6 +70,24 @@ def fp32_region(fn):
 AMP_COMPUTE = [__import__("os").environ.get("SEGSDE_AMP_COMPUTE", "f32").lower()]
 
 
+class conv_compute:
+    """``with conv_compute("bf16x9"):`` -- the convolutions called inside run their direct (implicit-GEMM) launches in that operand
+    arithmetic (hipops.CONV_COMPUTE: "f32" or "bf16x9"); the previous mode is restored on exit.  The mode is read when a
+    convolution is called (forward); its backward uses the same one."""
+
+    def __init__(self, mode):
+        self.mode = H.conv_compute_mode(mode)
+
+    def __enter__(self):
+        self.old = H.CONV_COMPUTE[0]
+        H.CONV_COMPUTE[0] = self.mode
+        return self
+
+    def __exit__(self, *exc):
+        H.CONV_COMPUTE[0] = self.old
+        return False
+
+
 def fusion(kind, taken):
     c = FUSIONS.setdefault(kind, [0, 0])
     c[0 if taken else 1] += 1

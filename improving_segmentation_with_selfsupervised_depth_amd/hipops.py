@@ -121,7 +121,7 @@ def winograd_ok(g, B=None, H=None, W=None, dgrad=False):
     transforms' traffic eats the 2.25x fewer multiply-adds.  The multiply-add floor keeps tiny launches (and the small-shape
     golden tests of the direct kernels) on the direct route.  Forward: one or two sources, zero / mirrored padding (mirrored:
     dilation 1), any dilation that divides the map into even sub-lattices.  Data-gradient: one source, zero padding."""
-    if g.compute:
+    if g.compute == 1:       # (the split-bf16 mode, 2, keeps its Winograd routes: fp32 arithmetic either way)
         return False
     cin, cout = (g.Cout, g.C0) if dgrad else (g.Cin, g.Cout)      # the data-gradient is the convolution Cout -> C0
     if not (WINOGRAD and g.k == 3 and g.stride == 1 and g.pad == g.dil and not g.up0 and g.cin_alg is None and g.C0 % 4 == 0
@@ -279,7 +279,7 @@ def winograd_fused_ok(g, B=None, H=None, W=None, dgrad=False):
     One source at output resolution: up to WINO_FUSED_MAX_CH channels, zero or mirrored padding, forward and data-gradient
     (mirrored: + segsde_reflect_adjoint_borders).  Forward on [upsample(x0) | x1] (g.up0): C0 % 64 == 0, up to
     WINO_FUSED2_MAX_CIN input channels, when the folded route's multiply-add share is above WINO_FUSED2_MIN_FOLD."""
-    if g.compute:
+    if g.compute == 1:
         return False
     cin, cout = (g.Cout, g.C0) if dgrad else (g.Cin, g.Cout)
     if not (WINOGRAD and WINO_FUSED and g.k == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1 and g.cin_alg is None
@@ -301,7 +301,7 @@ def winograd_fused_ok(g, B=None, H=None, W=None, dgrad=False):
 def winograd_fused_dgrad2_ok(g, B=None, H=None, W=None):
     """the skip-source data-gradient of a [upsample(x0) | x1] -> Cout mirrored 3x3 convolution as the one-kernel Winograd
     convolution Cout -> C1 (+ border kernel)"""
-    if g.compute:
+    if g.compute == 1:
         return False
     if not (WINOGRAD and WINO_FUSED and WINO_FUSED_DGRAD_EXT and WINO_FUSED_DGRAD2 and BORDERS2 and g.k == 3 and g.stride == 1 and g.dil == 1
             and g.pad == 1 and g.reflect and g.up0 and g.C1 and g.cin_alg is None and g.C1 % 64 == 0 and g.Cout % 64 == 0
@@ -452,7 +452,7 @@ WINO_FUSED_WGRAD_MIN_FOLD = float(os.environ.get("SEGSDE_WINO_FUSED_WGRAD_MIN_FO
 
 
 def winograd_fused_wgrad_ok(g, B=None, H=None, W=None):
-    if g.compute:            # half-precision operand mode: the direct / folded kernels (ConvGeom.compute)
+    if g.compute == 1:       # half-precision operand mode: the direct / folded kernels (ConvGeom.compute)
         return False
     if not (WINOGRAD and WINO_FUSED and WINO_FUSED_WGRAD and g.k == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1
             and g.cin_alg is None and g.C0 % 32 == 0 and g.C1 % 32 == 0 and g.Cout % 64 == 0 and g.Cout <= WINO_FUSED_WGRAD_MAX_CH):
@@ -499,6 +499,33 @@ def _tag(g, H, W):
                                                 " refl" if g.reflect else "")
 PAD_ZERO, PAD_REFLECT, PAD_REFLECT_ADJOINT = 0, 1, 2
 COMPUTE_F16 = [False]      # see ConvGeom.compute
+# Operand arithmetic of the fp32 convolutions that run on the direct (implicit-GEMM) kernels, read once at import from
+# SEGSDE_CONV_COMPUTE and switched by functional.conv_compute: "f32" (default) exact fp32 products on v_mfma_f32_32x32x2_f32;
+# "bf16x9": every operand split into three bf16 numbers that sum to it exactly, nine bf16 products per fp32 product on
+# v_mfma_f32_32x32x16_bf16 with fp32 accumulation (segsde_conv_desc.compute = 2): fp32 re-associated, not reduced precision.
+# The Winograd routes stay taken as with "f32".  "bf16x6" (six products, terms <= 2^-24 of a product dropped; compute = 3) is
+# a known name that is refused: measured 0.96-1.34x the fp32 launches, but it missed its error gate (profiles/split_bf16_layers.md).
+CONV_COMPUTE_MODES = {"f32": 0, "bf16x9": 2}
+
+
+def conv_compute_mode(name):
+    if name == "bf16x6":
+        raise ValueError("SEGSDE_CONV_COMPUTE / conv_compute: 'bf16x6' missed its error gate on the MI355X (max error 1.66x the "
+                         "fp32 kernel's, gate 1.5x) and is not shipped; of 'f32', 'bf16x9', 'bf16x6' use 'f32' or 'bf16x9'")
+    if name not in CONV_COMPUTE_MODES:
+        raise ValueError("SEGSDE_CONV_COMPUTE / conv_compute: %r is not one of 'f32', 'bf16x9', 'bf16x6'" % (name,))
+    return name
+
+
+CONV_COMPUTE = [conv_compute_mode(os.environ.get("SEGSDE_CONV_COMPUTE", "f32"))]
+# diagnostics / tests: direct launches made in the split-bf16 mode whose descriptor -- the one handed to the launch -- takes
+# the split loop (segsde_conv_compute_taken); nothing is counted, or asked, with the switch off
+CONV_COMPUTE_TAKEN = {"fwd": 0, "dgrad": 0, "wgrad": 0}
+
+
+def _note_compute(d, code, kind):
+    if d.compute >= 2 and _lib.lib().segsde_conv_compute_taken(ctypes.byref(d), code) == d.compute:
+        CONV_COMPUTE_TAKEN[kind] += 1
 
 
 # the current stream's handle straight from the C binding (torch.cuda.current_stream(device).cuda_stream builds a Stream object
@@ -556,8 +583,9 @@ class ConvGeom:
         self.stride, self.dil, self.pad, self.reflect, self.up0 = int(stride), int(dil), int(pad), bool(reflect), bool(up0)
         # segsde_conv_desc.compute of every launch of this convolution (forward, data-gradient, weight gradient): 1 under the
         # half-precision operand mode of `amp: True` (COMPUTE_F16, set by functional.fp32_region), where the Winograd routes --
-        # fp32 kernels, and 16 / 36 of the multiply-adds at 1 / 16 of the fp16 matrix rate -- are not taken
-        self.compute = 1 if COMPUTE_F16[0] else 0
+        # fp32 kernels, and 16 / 36 of the multiply-adds at 1 / 16 of the fp16 matrix rate -- are not taken; else 2 in the
+        # split-bf16 mode (CONV_COMPUTE), 0 by default
+        self.compute = 1 if COMPUTE_F16[0] else CONV_COMPUTE_MODES[CONV_COMPUTE[0]]
         if reflect and (self.k != 3 or self.stride != 1 or self.dil != 1 or self.pad != 1):
             raise NotImplementedError("reflection padding is implemented for the reference's 3x3/s1/p1 Conv3x3 only")
 
@@ -667,6 +695,7 @@ def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=Non
             executed=flops * _fold_frac(g))
         if rc == 0:
             UPFOLD_TAKEN["fwd"] += 1
+            _note_compute(d, 4, "fwd")
             return y
         if rc != -4:
             check(rc, "conv2d_forward_upfold")
@@ -678,6 +707,7 @@ def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=Non
     _timed("conv_fwd", flops, x0, lambda: check(_lib.lib().segsde_conv2d_forward_stats(
         ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(bias), _p(y), None, _p(part), _stream(x0)), "conv2d_forward"),
         _tag(g, H, W), executed=flops_x)
+    _note_compute(d, 0, "fwd")
     return (y, part) if want_stats else y
 
 
@@ -758,6 +788,7 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         if rc == -4:
             return None, None
         check(rc, "conv2d dgrad (accumulate)")
+        _note_compute(d, 1, "dgrad")
         ACTGRAD_FUSED[0] = actgrad is not None
         return acc, None
     if g.up0 and fold is not None and accumulate_into is None:
@@ -802,6 +833,7 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
             _p(ag_y) if dx0 is not None else None, ag_ld, ag_kind, _stream(dy)), _tag(g, H, W) + " fold", executed=flops * fr)
         if rc == 0:
             UPFOLD_TAKEN["dgrad"] += 1
+            _note_compute(df, 5, "dgrad")
             SKIP_ACCUMULATED[0] = acc1 is not None
             ACTGRAD_FUSED[0] = actgrad is not None and dx0 is not None
             return dx0, (w1 if w1 is not None else dx1f)
@@ -816,10 +848,12 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         rc = _timed("conv_dgrad", flops, dy, lambda: launch(d, dx0, dx1, actgrad is not None), _tag(g, H, W))
         if rc == 0:
             ACTGRAD_FUSED[0] = actgrad is not None
+            _note_compute(d, 1, "dgrad")
             return dx0, dx1
         if rc == -4 and actgrad is not None:
             rc = launch(d, dx0, dx1, False)
             if rc == 0:
+                _note_compute(d, 1, "dgrad")
                 return finish_unfused(dx0), dx1
         if rc != -4:
             check(rc, "conv2d dgrad (fused upsample adjoint)")
@@ -831,6 +865,7 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         fused = False
         rc = launch(d, full0, dx1, False)
     check(rc, "conv2d dgrad")
+    _note_compute(d, 1, "dgrad")
     if g.up0:
         dx0 = torch.empty((B, H // 2, W // 2, g.C0), dtype=torch.float32, device=dy.device)
         check(L.segsde_upsample2x_backward(_p(full0), g.C0, B, H // 2, W // 2, g.C0, _p(dx0), g.C0, _stream(dy)),
@@ -894,6 +929,7 @@ def conv_wgrad(g, x0, x1, dy, wino_v=None, out=None):
                 _tag(g, H, W) + " fold", executed=flops * _fold_frac(g))
             if rc == 0:
                 UPFOLD_TAKEN["wgrad"] += 1
+                _note_compute(d, 6, "wgrad")
                 return dw
             if rc != -4:
                 check(rc, "conv2d_wgrad_upfold")
@@ -902,7 +938,35 @@ def conv_wgrad(g, x0, x1, dy, wino_v=None, out=None):
     _timed("conv_wgrad", flops, dy, lambda: check(L.segsde_conv2d_wgrad(
         ctypes.byref(d), _p(x0), _p(x1), _p(_f32(dy)), nhwc_ld(dy), _p(dw), _p(ws), nbytes, _stream(dy)), "conv2d_wgrad"),
         _tag(g, H, W), executed=flops_x)
+    _note_compute(d, 2, "wgrad")
     return dw
+
+
+def conv_compute_taken(g, B, H, W, direction, fold=False):
+    """The operand arithmetic (0 fp32, 1 fp16, 2 split bf16) the DIRECT kernels will run convolution g in on a [B, H, W] virtual
+    input with dense tensors (segsde_conv_compute_taken: the launchers' own dispatch, nothing is launched).  direction: "fwd",
+    "dgrad", "wgrad"; fold: the upsample-folded entry point of that direction (g.up0).  Says nothing about the Winograd routes,
+    which are fp32 kernels and are chosen before the direct ones (winograd_ok, winograd_fused_ok ...)."""
+    Ho, Wo = g.out_hw(H, W)
+    pm = PAD_REFLECT if g.reflect else PAD_ZERO
+    code = {"fwd": 0, "dgrad": 1, "wgrad": 2}[direction] | (4 if fold else 0)
+    if direction == "dgrad" and not fold:
+        d = ConvDesc(B=B, H=Ho, W=Wo, C0=g.Cout, C1=0, ld0=g.Cout, ld1=0, up0=0, Ho=H, Wo=W, Cout=g.Cin, ldy=g.C0, ldy2=g.C1, nsplit=g.C0,
+                     KH=g.k, KW=g.k, stride=1, dil=g.dil, pad=(g.k - 1) * g.dil - g.pad, pad_mode=PAD_REFLECT_ADJOINT if g.reflect else PAD_ZERO,
+                     in_div=g.stride, act=0, sum2x2=0, accumulate=0, compute=g.compute)
+    else:
+        d = ConvDesc(B=B, H=H, W=W, C0=g.C0, C1=g.C1, ld0=g.C0, ld1=g.C1, up0=int(g.up0), Ho=Ho, Wo=Wo, Cout=g.Cout, ldy=g.Cout, ldy2=0,
+                     nsplit=0, KH=g.k, KW=g.k, stride=g.stride, dil=g.dil, pad=g.pad, pad_mode=pm, in_div=1, act=0, sum2x2=0, compute=g.compute)
+    return int(_lib.lib().segsde_conv_compute_taken(ctypes.byref(d), code))
+
+
+def split_bf16(x):
+    """(h, m, l): the three bf16 numbers (as float32 tensors of x's shape) the split-bf16 convolution loops make of every fp32
+    operand, h + m + l == x exactly (segsde_split_bf16_planes)"""
+    x = _f32(x).contiguous()
+    out = [torch.empty(x.shape, dtype=torch.int16, device=x.device) for _ in range(3)]
+    check(_lib.lib().segsde_split_bf16_planes(_p(x), x.numel(), _p(out[0]), _p(out[1]), _p(out[2]), _stream(x)), "split_bf16_planes")
+    return tuple((t.to(torch.int32) << 16).view(torch.float32) for t in out)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 14
+#define SEGSDE_ABI_VERSION 15
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -58,8 +58,29 @@ typedef struct segsde_conv_desc {
   int compute;      /* 0: fp32 operands (exact fp32 products, the judged arithmetic).  1: the operands are rounded to fp16
                        inside the kernel and multiplied on v_mfma_f32_32x32x16_f16 with fp32 accumulation -- what
                        torch.cuda.amp.autocast makes of the reference's convolutions under `amp: True` (train.py:468,502).
-                       Launches whose shape does not take the LDS-DMA loop compute in fp32 whatever this says.            */
+                       2: split-bf16 operands -- every fp32 operand is split inside the kernel into three bf16 numbers whose sum
+                       is the operand exactly (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m), round to nearest even) and the
+                       product becomes nine bf16 x bf16 products, each exact in fp32, accumulated in fp32 by
+                       v_mfma_f32_32x32x16_bf16: fp32 re-associated, not reduced precision.  A non-finite operand gives a
+                       non-finite (NaN) result; operands below 2^-108 lose their low terms (bf16 underflow).
+                       3: reserved for the six-product form (h.h, h.m, m.h, h.l, l.h, m.m; the dropped terms are <= 2^-24 of a
+                       product each), which missed its error gate on the hardware: every entry point returns
+                       SEGSDE_ERR_UNSUPPORTED for it.
+                       Launches whose shape does not take the LDS-DMA loop compute in fp32 whatever this says
+                       (segsde_conv_compute_taken tells).                                                                  */
 } segsde_conv_desc;
+
+/* The operand arithmetic (a value of segsde_conv_desc.compute) the launchers WILL use for d, from the predicates they dispatch
+ * on.  direction: which entry point d is meant for -- SEGSDE_DIR_FORWARD / SEGSDE_DIR_DGRAD: segsde_conv2d_forward* /
+ * segsde_conv2d_dgrad_actgrad (d as handed to that call), SEGSDE_DIR_WGRAD: segsde_conv2d_wgrad; | SEGSDE_DIR_UPFOLD: the
+ * segsde_conv2d_*_upfold call of that direction (d: the forward geometry).  Evaluated for 16-byte aligned tensors with dense rows.
+ * d->compute if every implicit-GEMM launch of the call takes it; 0 if any computes in fp32, the call takes another kernel
+ * (the one-channel stencils) or rejects d.  Host only: nothing is launched. */
+enum { SEGSDE_DIR_FORWARD = 0, SEGSDE_DIR_DGRAD = 1, SEGSDE_DIR_WGRAD = 2, SEGSDE_DIR_UPFOLD = 4 };
+int segsde_conv_compute_taken(const segsde_conv_desc* d, int direction);
+/* The operand split of the compute = 2 loops applied to an array (tests, probes): h[i], m[i], l[i] = the bf16 bit patterns with
+ * float(h[i]) + float(m[i]) + float(l[i]) == x[i] exactly for finite x[i] of magnitude in [2^-108, 2^128 - 2^119). */
+int segsde_split_bf16_planes(const float* x, long n, unsigned short* h, unsigned short* m, unsigned short* l, void* stream);
 
 /* y[b,ho,wo,n] = act(bias[n] + sum_{kh,kw,c} x[b, ho*stride-pad+kh*dil, wo*stride-pad+kw*dil, c] * wpack[n][kh][kw][c])
  * Replaces: every nn.Conv2d on the path -- torchvision ResNet convs reached from models/resnet_encoder.py:93-99,
