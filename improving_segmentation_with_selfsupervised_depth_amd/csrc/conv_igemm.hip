@@ -76,7 +76,6 @@ struct ConvP {
   // Grouped weights (the sixteen position GEMMs of a Winograd convolution as one launch, FAST / LDS-DMA path only): a tile
   // whose first row lies in image b of the B-image input reads its weight rows from w + b * wbstride floats.  0: one weight.
   long wbstride;
-  int nt;       // 1: the staged epilogue's full-tile stores are streaming stores (set by the launcher for outputs beyond the caches)
   int cmp;      // operand arithmetic asked of the LDS-DMA loops (segsde_conv_desc.compute): 1 fp16, 2 split bf16 (nine products)
 };
 constexpr int SEGSDE_PAD_CLAMP_ = 3;   // internal (never crosses the ABI)
@@ -199,7 +198,10 @@ __device__ __forceinline__ float4 fetch_w4(const ConvP& p, int n, int k) {
   return v;
 }
 
-// reduction elements per staged chunk: template parameter BK (32, or 64 on the FAST path when channels allow)
+// Reduction elements per staged chunk.  64-deep chunks (139 KB of LDS, one workgroup per CU, half the barriers) lost 15-25 % on the
+// large layers against 32 with two co-resident workgroups per CU (profiles/ab_conv_r01.log); 16-deep chunks with four LDS stages or
+// three workgroups per CU lost as well (profiles/experiments_r02.md).
+constexpr int BK = 32;
 
 // ---------------------------------------------------------------------------------------------------
 // forward / data-gradient kernel
@@ -255,12 +257,11 @@ __device__ __forceinline__ float4 fast_fetch(const ConvP& p, const SrcSel& s, in
   return *reinterpret_cast<const float4*>(ptr);
 }
 
-// MODE 0: generic scalar gather, 1: generic float4 gather, 2: FAST (uniform tap per chunk, branch-free loads),
-// 3: FAST + reflection-pad adjoint extras, 4: FAST with the tiles written to LDS by the load itself (LDS-DMA)
-// VAR: experiment variants of the LDS-DMA loop (SEGSDE_TUNE="var=N"; 0 = shipped): 1 = all tile loads of a chunk issued
-// up front, 2 = no scheduling fences between the MFMA units, 3 = raised wave priority around the MFMA units, 4 = (with BK = 16)
-// four LDS stages: the loads of chunk k+3 are issued during chunk k, two chunks of loads stay in flight across barriers
-// VARX = VAR + 16 * CMP (MODE 4 only), CMP = segsde_conv_desc.compute of the instantiation.  CMP 1: HALF-PRECISION OPERANDS, the arithmetic of the reference's `amp: True` mode (torch autocast runs its
+// MODE 0: generic scalar gather, 1: generic float4 gather, 3: FAST (uniform tap per chunk, branch-free loads) + reflection-pad
+// adjoint extras, 4: FAST with the tiles written to LDS by the load itself (LDS-DMA).  (2 was the register-staged FAST loop as a
+// launch of its own; its loop body lives on in the bordered waves of MODE 3.)
+// CLAMP (MODE 4 only): out-of-range taps read the nearest border pixel (the upsample-folded class launches).
+// CMP (MODE 4 only) = segsde_conv_desc.compute of the instantiation.  CMP 1: HALF-PRECISION OPERANDS, the arithmetic of the reference's `amp: True` mode (torch autocast runs its
 // convolutions on fp16 inputs with fp32 accumulation).  Tiles still travel as fp32 (LDS-DMA cannot convert); a lane's two
 // fragment reads of a 16-deep k block (4 + 4 consecutive floats per operand row) are rounded to eight halves
 // (v_cvt_pk_f16_f32, round to nearest even) and ONE v_mfma_f32_32x32x16_f16 replaces eight v_mfma_f32_32x32x2_f32 -- which k
@@ -269,16 +270,15 @@ __device__ __forceinline__ float4 fast_fetch(const ConvP& p, const SrcSel& s, in
 // CMP 2: SPLIT-BF16 OPERANDS.  The same two fragment reads per operand row, each of the eight fp32 values split into three bf16
 // numbers that sum to it exactly (segsde_split_bf16, segsde_common.h: also what becomes of non-finite and tiny operands), and
 // NINE v_mfma_f32_32x32x16_bf16 per accumulator and k block, smallest products first -- fp32 re-associated, not reduced precision.
-template <int BM, int BN, int WM, int WN, int MODE, int BK, int VARX = 0>
-__global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kernel(ConvP p) {
-  constexpr int VAR = VARX & 15;
-  constexpr int CMP = VARX >> 4;            // segsde_conv_desc.compute of this instantiation
+template <int BM, int BN, int WM, int WN, int MODE, bool CLAMP = false, int CMP = 0>
+__global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvP p) {
   constexpr bool F16 = CMP == 1, SPLIT = CMP == 2;
-  static_assert(CMP <= 2 && (CMP == 0 || MODE == 4), "half-precision / split-bf16 operands: LDS-DMA loop only");
+  static_assert(MODE == 0 || MODE == 1 || MODE == 3 || MODE == 4, "MODE 2 (register-staged FAST launch) is retired");
+  static_assert(CMP <= 2 && (MODE == 4 || (CMP == 0 && !CLAMP)), "clamp padding, half-precision / split-bf16 operands: LDS-DMA loop only");
   constexpr bool VEC = MODE >= 1;
   constexpr bool FAST = MODE >= 2;
   constexpr bool ADJ = MODE == 3;
-  constexpr bool DMA = MODE == 4 || (MODE == 3 && VAR != 5);   // MODE 3: the waves that own no border pixel run the LDS-DMA loop too
+  constexpr bool DMA = MODE == 4 || MODE == 3;   // MODE 3: the waves that own no border pixel run the LDS-DMA loop too
   // LDS rows are unpadded (BK floats); the 16-byte column groups of a row are XOR-swizzled with the row index so that
   // the 16 lanes of every ds_read_b128 lane group hit 16 distinct 16-byte slots of the 256-byte bank row (conflict-free)
   // -- no padding means 48 KB instead of 54 KB for the 128x64 tile, i.e. THREE workgroups per CU instead of two.
@@ -289,9 +289,8 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
   constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
   constexpr int AR = BM / RP, BR = BN / RP;
   constexpr int STAGE = (BM + BN) * LDT;
-  constexpr int NSTAGES = VAR == 4 ? 4 : 2;
-  // floats of LDS in front of the FAST path's tap table: the stages or the staged epilogue's tile, whichever is larger
-  constexpr int TAB0 = NSTAGES * STAGE > BM * BN ? NSTAGES * STAGE : BM * BN;
+  // floats of LDS in front of the FAST path's tap table: the two stages or the staged epilogue's tile, whichever is larger
+  constexpr int TAB0 = 2 * STAGE > BM * BN ? 2 * STAGE : BM * BN;
   static_assert(WM * WN == 4, "4 waves per workgroup");
   SEGSDE_SMEM;
   float* smem = reinterpret_cast<float*>(segsde_smem);
@@ -486,9 +485,9 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
       const int sh = in0 ? s0.shift : 0;
       const unsigned ld = in0 ? s0.ld : s1.ld, Ws = in0 ? s0.Ws : s1.Ws, bst = in0 ? s0.bstride : s1.bstride;
       const int ds = p.in_div >> 1;   // data-gradient of a stride-2 conv: only even coordinates carry a value
-      // clamp padding (upsample-folded class launches) is a compile-time variant, VAR = 9: as one more run-time flag it cost the
+      // clamp padding (upsample-folded class launches) is a compile-time variant: as one more run-time flag it cost the
       // K loops their last free SGPRs (the LDS-DMA operands no longer got scalar registers)
-      constexpr bool clampm = VAR == 9;
+      constexpr bool clampm = CLAMP;
       const bool refl = !clampm && p.pad_mode == SEGSDE_PAD_REFLECT;
 #pragma unroll
       for (int i = 0; i < AR; ++i) {
@@ -530,7 +529,7 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
     // bordered wave's tap change is table reads as well (every chunk ends in a barrier: the one wave per tile that
     // recomputed ~250 VALU of offsets per tap set the pace).  The 128x64 tile would lose its third workgroup per CU to
     // the 4.6 KB, and a wave that owns a corner-adjacent pixel (up to three extras) keeps recomputing.
-    constexpr bool XTAB = ADJ && BN >= 128 && VAR != 8;   // var=8: A/B knob
+    constexpr bool XTAB = ADJ && BN >= 128;
     const bool xtab = XTAB && p.W >= 128;   // narrow images: every wave is bordered, building the second bank costs more than it saves
     // The extra pre-image of a border row from its MAIN offset (adjoint: 3x3, pad 1, one source at full resolution): row 1
     // with the tap dh = +1 reads row 2 and also collects row 0, two rows up; row H-2 with dh = -1 two rows down; columns
@@ -653,8 +652,6 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
         // the barrier that ends iteration kc.  No ds_write, no staging VGPRs, the loop body has no vector memory
         // instruction that returns to registers.
         static_assert(KQ == 8 || KQ == 4, "an LDS-DMA piece is 1 KiB: 8 rows x 128 bytes or 16 rows x 64 bytes");
-        constexpr int NST = VAR == 4 ? 4 : 2;                  // LDS stages; loads run NST-1 chunks ahead of the MFMAs
-        constexpr int INFLIGHT = (NST - 2) * (AR + BR);        // loads allowed to stay outstanding at a chunk's barrier
         // LDS byte address of this wave's 1 KiB piece in pass 0 of the A tile of stage 0 (scalar from here on)
         const unsigned lds0 = segsde_lds_addr(smem) + (unsigned)(__builtin_amdgcn_readfirstlane(wave) * 1024);
         constexpr unsigned PASS = RP * LDT * 4, BOFF = BM * LDT * 4, STG = STAGE * 4;
@@ -678,17 +675,14 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
         auto dmaA = [&](unsigned stage, int i) { segsde_buffer_load4_lds(rsa, voff[i], soffA, lds0 + stage + PASS * i); };
         auto dmaB = [&](unsigned stage, int i) { segsde_buffer_load4_lds(rsw, voffB[i], soffB, lds0 + stage + BOFF + PASS * i); };
         tap_update(wadj_tag, true);
+        dma_begin();                                           // chunk 0 into stage 0
   #pragma unroll
-        for (int j = 0; j < NST - 1; ++j) {                    // chunks 0 .. NST-2
-          dma_begin();
+        for (int i = 0; i < AR; ++i) dmaA(0u, i);
   #pragma unroll
-          for (int i = 0; i < AR; ++i) dmaA((unsigned)j * STG, i);
-  #pragma unroll
-          for (int i = 0; i < BR; ++i) dmaB((unsigned)j * STG, i);
-          dma_end(j + 1 < nchunks, true);
-        }
+        for (int i = 0; i < BR; ++i) dmaB(0u, i);
+        dma_end(1 < nchunks, true);
         tab_build(wadj_tag);                                   // under the latency of the first loads
-        segsde_wait_vmcnt<INFLIGHT>();                         // chunk 0 has landed
+        segsde_wait_vmcnt0();                                  // chunk 0 has landed
         __syncthreads();
         const int arow = wm * TM * 32 + (lane & 31), brow = wn * TN * 32 + (lane & 31), h = lane >> 5;
         const int sa = swz(arow), sb = swz(brow);
@@ -702,7 +696,7 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
         };
         auto comp = [](const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); };
         constexpr int DSTEP = (U - 2) / (AR + BR) > 0 ? (U - 2) / (AR + BR) : 1;
-        // one chunk; buf is a compile-time constant in the two-stage loop (unrolled by two below) so that the fragment
+        // one chunk; buf is a compile-time constant (the loop is unrolled by two below) so that the fragment
         // reads and the LDS-DMA destinations use immediate offsets -- the 8 v_lshl_add_u32 per chunk that rebuilt the
         // stage base were most of the loop's remaining VALU work
         auto chunk = [&](int kc, auto buf_c, auto first_c) {
@@ -711,14 +705,7 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
                                                              // accumulators (inline constant) instead of 64 v_mov up front
           fread(buf, 0, 0);
           dma_begin();                     // past the last chunk: the last one is fetched again (harmless, waited for)
-          const unsigned stn = (unsigned)((buf + NST - 1) & (NST - 1)) * STG;
-          if constexpr (VAR == 1) {
-  #pragma unroll
-            for (int i = 0; i < AR; ++i) dmaA(stn, i);
-  #pragma unroll
-            for (int i = 0; i < BR; ++i) dmaB(stn, i);
-          }
-          if constexpr (VAR == 3) __builtin_amdgcn_s_setprio(1);
+          const unsigned stn = (unsigned)(buf ^ 1) * STG;
   #pragma unroll
           for (int u = 0; u < U; ++u) {
             const int g = u / 4, st = u % 4;
@@ -761,34 +748,25 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(fa[g & 1][i], st), comp(fb[g & 1][j], st),
                                                                  (FIRST && u == 0) ? f32x16{} : acc[i][j], 0, 0, 0);
             }
-            if constexpr (VAR != 1) {
+            // the tile loads dealt out between the MFMA units, a scheduling fence after each unit (all loads up front, no
+            // fences, raised wave priority: each measured slower or equal, profiles/experiments_r02.md)
   #pragma unroll
-              for (int i = 0; i < AR; ++i)
-                if (u == DSTEP * i) dmaA(stn, i);
+            for (int i = 0; i < AR; ++i)
+              if (u == DSTEP * i) dmaA(stn, i);
   #pragma unroll
-              for (int i = 0; i < BR; ++i)
-                if (u == DSTEP * (AR + i)) dmaB(stn, i);
-            }
-            if constexpr (VAR != 2) __builtin_amdgcn_sched_barrier(0);
+            for (int i = 0; i < BR; ++i)
+              if (u == DSTEP * (AR + i)) dmaB(stn, i);
+            __builtin_amdgcn_sched_barrier(0);
           }
-          if constexpr (VAR == 3) __builtin_amdgcn_s_setprio(0);
-          dma_end(kc + NST < nchunks, false);
-          segsde_wait_vmcnt<INFLIGHT>();   // chunk kc+1 has landed (later chunks may still be in flight)
+          dma_end(kc + 2 < nchunks, false);
+          segsde_wait_vmcnt0();            // chunk kc+1 has landed
           __syncthreads();
         };
-        if constexpr (NST == 2 && VAR != 7) {   // var=7: A/B knob (round-2 loop before this unroll and the kernarg refresh)
-          chunk(0, std::integral_constant<int, 0>{}, std::true_type{});
-          if (1 < nchunks) chunk(1, std::integral_constant<int, 1>{}, std::false_type{});
-          for (int kc = 2; kc < nchunks; kc += 2) {
-            chunk(kc, std::integral_constant<int, 0>{}, std::false_type{});
-            if (kc + 1 < nchunks) chunk(kc + 1, std::integral_constant<int, 1>{}, std::false_type{});
-          }
-        } else {
-          for (int kc = 0; kc < nchunks; ++kc) chunk(kc, kc & (NST - 1), std::false_type{});
-        }
-        if constexpr (INFLIGHT > 0) {      // the epilogue reuses the stages: nothing may still be landing
-          segsde_wait_vmcnt0();
-          __syncthreads();
+        chunk(0, std::integral_constant<int, 0>{}, std::true_type{});
+        if (1 < nchunks) chunk(1, std::integral_constant<int, 1>{}, std::false_type{});
+        for (int kc = 2; kc < nchunks; kc += 2) {
+          chunk(kc, std::integral_constant<int, 0>{}, std::false_type{});
+          if (kc + 1 < nchunks) chunk(kc + 1, std::integral_constant<int, 1>{}, std::false_type{});
         }
         return;
       }
@@ -865,7 +843,7 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
   // The epilogue's parameters (destinations, pitches, split point, statistics / activation-gradient pointers ...) are
   // re-read from the kernel-argument segment HERE: held in SGPRs across the K loop they pushed the adjoint kernel over the
   // SGPR budget -- 16 v_readlane + 2 scratch accesses per chunk inside its loop (and every VALU cycle is a matrix cycle).
-  const ConvP pe = VAR == 7 ? p : SEGSDE_REFRESH_KERNARG(ConvP, p);   // var=7: A/B knob, no refresh
+  const ConvP pe = SEGSDE_REFRESH_KERNARG(ConvP, p);
   // epilogue, staged variant: the accumulator tile goes through LDS (free after the K loop) so that every output row
   // leaves as 16-byte stores covering whole 512-byte (BN*4) row segments, instead of 4-byte stores per lane -- the
   // short-K layers (1x1 bottleneck convs and their gradients) are bound by exactly this store stream.
@@ -992,7 +970,7 @@ __global__ __launch_bounds__(256, (VARX & 15) == 6 ? 3 : 2) void conv_igemm_kern
             v.z *= segsde_act_grad_from_out(yv.z, pe.agkind); v.w *= segsde_act_grad_from_out(yv.w, pe.agkind);
           }
           if (pe.accum) { v.x += o[t].x; v.y += o[t].y; v.z += o[t].z; v.w += o[t].w; }
-          if (pe.nt) segsde_buffer_store4_nt(rd, vo, so, v); else segsde_buffer_store4(rd, vo, so, v);
+          segsde_buffer_store4(rd, vo, so, v);   // (streaming stores for outputs beyond the caches: +-0, profiles/experiments_r06.md)
           so += step; soa += stepa;
         }
         return;
@@ -1174,36 +1152,30 @@ __device__ __forceinline__ void wgrad_k_decode(int k, int Ctot, int taps, int sr
 
 constexpr int BP = 32;  // pixels per staged chunk
 
-// Reduction of the split partials inside the weight-gradient kernel (round-3 EXPERIMENT, off by default: SEGSDE_TUNE="wred=1").
-// Every workgroup stores its partial slab, fences, and takes a ticket of its (k-tile, n-tile); the workgroup that draws the
-// LAST ticket sums all slabs of the tile in slab order -- the same order whichever workgroup does it, so the result is
-// deterministic -- writes OIHW and puts the ticket back to zero.  Correct (119 GPU tests), but MEASURED SLOWER: the
-// device-scope release fence every workgroup needs writes its XCD's whole L2 back (8 XCDs, no cross-XCD L2 coherence):
-// conv_wgrad 398 -> 648 us per launch, the step 334 -> 420 ms together with the same trick in the column reductions
-// (profiles/experiments_r03.md).  A kernel boundary pays that write-back once per launch; the 184 wgrad_reduce launches of
-// ~14 us stay.  tickets == nullptr (default): partial slabs only, a separate reduce kernel follows.
-struct WRed { unsigned* tickets; float* dw; int CtotDst, cOff, taps, srcC0; };
+// The split partials are reduced by a separate kernel (wgrad_reduce_kernel), not by the last workgroup of each tile: an in-kernel
+// reduction needs a device-scope release fence in every workgroup, which writes its XCD's whole L2 back (8 XCDs, no cross-XCD L2
+// coherence) -- conv_wgrad 398 -> 648 us per launch, the step 334 -> 420 ms together with the same trick in the column reductions
+// (profiles/experiments_r03.md).  A kernel boundary pays that write-back once per launch; the ~14 us reduce launches stay.
 
-// MODEX = MODE + 16 * CMP (with MODE 5), CMP as in conv_igemm_kernel.  CMP 1: half-precision operands -- the eight scalars a lane reads for
+// CMP (with MODE 5) as in conv_igemm_kernel.  CMP 1: half-precision operands -- the eight scalars a lane reads for
 // eight consecutive fp32 MFMAs of a 16-pixel block (pixels 2 u + lane half of two fragment groups) become ONE operand of
 // v_mfma_f32_32x32x16_f16; both operands are read with the same pattern, so the k slots agree.  CMP 2: split-bf16 operands, the
 // same eight scalars split into three bf16 operands each, nine v_mfma_f32_32x32x16_bf16 per accumulator
-template <int BKT, int BN, int WM, int WN, int MODEX>
+template <int BKT, int BN, int WM, int WN, int MODE, int CMP = 0>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float* dy, int lddy, float* part,
-                                                         int chunks_per_split, WRed wr) {
-  constexpr int MODE = MODEX & 15;
-  constexpr int CMP = MODEX >> 4;           // segsde_conv_desc.compute of this instantiation
+                                                         int chunks_per_split) {
   constexpr bool F16 = CMP == 1, SPLIT = CMP == 2;
+  static_assert(MODE == 0 || MODE == 1 || MODE == 3 || MODE == 5, "MODE 2 / 4 (earlier table-driven loops) are retired");
   static_assert(CMP <= 2 && (CMP == 0 || MODE == 5), "half-precision / split-bf16 operands: the pipelined LDS-DMA loop only");
-  // MODE 0: scalar gather, 1: float4 gather, 2: FAST A side + vector dY + rows at least 32 pixels wide (straight-line
-  // loop), 3: FAST A side with the general row walk / scalar dY (odd Cout, tiny feature maps), 4: MODE 2 with the tile
-  // loads writing LDS themselves (LDS-DMA, see the forward kernel), 5: MODE 4 with the chunk's barrier moved into the chunk
-  // (round 4: tile loads run two chunks ahead, the first fragments of the next chunk are read before the chunk boundary)
+  // MODE 0: scalar gather, 1: float4 gather, 3: FAST A side with the general row walk / scalar dY (odd Cout, tiny feature
+  // maps), 5: table-driven FAST A side + vector dY + rows a multiple of 32 pixels wide, the tile loads writing LDS themselves
+  // (LDS-DMA, see the forward kernel) and the chunk's barrier inside the chunk (tile loads run two chunks ahead, the first
+  // fragments of the next chunk are read before the chunk boundary).  (2 and 4 were that loader register-staged / with the
+  // barrier at the chunk boundary: profiles/ab_r02_wgrad_lds_dma.log, profiles/ab_r04_wgrad_pipe.log.)
   constexpr bool VEC = MODE >= 1;
   constexpr bool FAST = MODE >= 2;
-  constexpr bool SIMPLE = MODE == 2 || MODE == 4 || MODE == 5;
-  constexpr bool DMA = MODE == 4 || MODE == 5;
-  constexpr bool PIPE = MODE == 5;
+  constexpr bool SIMPLE = MODE == 5;   // the table-driven loader
+  constexpr bool DMA = MODE == 5;
   constexpr int TM = BKT / (WM * 32), TN = BN / (WN * 32);
   constexpr int AQ = BKT / 4, DQ = BN / 4;             // float4 columns per tile row
   constexpr int AI = (BP * AQ) / 256, DI = (BP * DQ) / 256;
@@ -1254,7 +1226,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
       decode_m(p, fm[i], fb[i], fh[i], fw[i], ok);   // fh/fw are ho*stride, wo*stride
     }
   }
-  // MODE 2 (Wo % 32 == 0: a chunk is 32 consecutive pixels of ONE image row): the A-side offsets come from four small
+  // MODE 5 (Wo % 32 == 0: a chunk is 32 consecutive pixels of ONE image row): the A-side offsets come from four small
   // LDS tables -- byte offset of padded input row hi / column wi inside one image of source 0 / 1, or TAB_MARK on zero
   // padding -- so that a chunk's tile loads cost ~10 VALU instructions per thread instead of ~180 (fp32 MFMA and VALU
   // share issue cycles on gfx950).  voff = Htab[h*stride + kh*dil] + Wtab[(w0 + row)*stride + kw*dil] + channel; the
@@ -1314,7 +1286,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
 
   float4 ra[AI], rd[DI];
   const bool wide = SIMPLE || p.Wo >= BP;   // a 32-pixel step wraps at most one image row: carries, not divisions
-  // MODE 2 pieces of one chunk's tile loads, issued separately so they can be dealt out between the MFMA units
+  // MODE 5 pieces of one chunk's tile loads, issued separately so they can be dealt out between the MFMA units
   unsigned thv = 0, twv[AI];
   auto tload = [&]() {      // table lookups for the chunk at (cb, chh, cw)
     const char* tb = reinterpret_cast<const char*>(tabs);
@@ -1353,20 +1325,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
     const unsigned pix = (unsigned)((cb * p.OHf + p.os * chh + p.oph) * p.OWf + p.os * cw + p.opw);
     return dy + (size_t)pix * (unsigned)lddy;
   };
-  auto dload = [&](int c) {
-    const segsde_rsrc rd_ = segsde_make_rsrc(dybase(c), c < nchunks_total ? 0x7fffffffu : 0u);
-#pragma unroll
-    for (int i = 0; i < DI; ++i) rd[i] = segsde_buffer_load4(rd_, voffD[i], 0u);
-    cw += BP;
-    if (cw == p.Wo) { cw = 0; if (++chh == p.Ho) { chh = 0; ++cb; } }
-  };
-  auto gload = [&](int c) {
-    if constexpr (SIMPLE) {
-      tload();
-      aload(c);
-      dload(c);
-      return;
-    }
+  auto gload = [&](int c) {   // MODE 0 / 1 / 3
     if constexpr (FAST) {
 #pragma unroll
       for (int i = 0; i < AI; ++i) {
@@ -1543,10 +1502,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
       tload();
       issue(0u);
     }
-    int left = nlive - 1;                         // PIPE: live chunks whose tile loads are still to be issued
-    if constexpr (PIPE) {
-      if (left > 0) { tload(); issue(STG); --left; }
-    }
+    int left = nlive - 1;                         // live chunks whose tile loads are still to be issued
+    if (left > 0) { tload(); issue(STG); --left; }
     segsde_wait_vmcnt0();
     __syncthreads();
     float fa[2][4][TM], fd[2][4][TN];
@@ -1565,33 +1522,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
         for (int j = 0; j < TN; ++j) fd[slot][u][j] = St[dofs[j] + 2 * (4 * g + u) * BN];
       }
     };
-    // unrolled by two so that the stage index is a compile-time constant (immediate LDS offsets, no address VALU)
-    auto chunk = [&](auto buf_c) {
-      constexpr int buf = decltype(buf_c)::value;
-      fread(buf, 0, 0);
-      tload();
-#pragma unroll
-      for (int u = 0; u < BP / 2; ++u) {
-        const int g = u / 4, st = u % 4;
-        if (st == 2 && g + 1 < BP / 8) fread(buf, g + 1, (g + 1) & 1);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][st][i], fd[g & 1][st][j], acc[i][j], 0, 0, 0);
-        if (u == 1) issue((unsigned)(buf ^ 1) * STG);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      segsde_wait_vmcnt0();
-      __syncthreads();
-    };
-    // PIPE (MODE 5).  In the loop above every chunk ends in wait + barrier and the next one starts with the LDS reads of its
+    // With the barrier at the chunk boundary every chunk ends in wait + barrier and the next one starts with the LDS reads of its
     // first fragments: a read-latency chain right behind every barrier, on all four waves at once.  Here the barrier sits
     // INSIDE the chunk, after the wave's last fragment read of this stage (group 3 is read at unit 10): once every wave has
     // passed it, (a) this stage is free -- the tile loads of chunk c + 2 go into it right away (two chunks of lead instead of
     // one), and (b) the other stage (loads issued one chunk ago, waited for before the barrier) is visible -- the first
     // fragments of chunk c + 1 are read at unit 14, while the last MFMAs of chunk c still run.  Nothing waits at the chunk
-    // boundary any more; still one barrier per chunk.
+    // boundary any more; still one barrier per chunk.  Unrolled by two so that the stage index is a compile-time constant
+    // (immediate LDS offsets, no address VALU).
     auto pchunk = [&](auto buf_c) {
       constexpr int buf = decltype(buf_c)::value;
 #pragma unroll
@@ -1646,70 +1584,24 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    if constexpr (PIPE) {
-      fread(0, 0, 0);
-      for (int i = 0; i < nlive; i += 2) {
-        pchunk(std::integral_constant<int, 0>{});
-        if (i + 1 < nlive) pchunk(std::integral_constant<int, 1>{});
-      }
-    } else
+    fread(0, 0, 0);
     for (int i = 0; i < nlive; i += 2) {
-      chunk(std::integral_constant<int, 0>{});
-      if (i + 1 < nlive) chunk(std::integral_constant<int, 1>{});
+      pchunk(std::integral_constant<int, 0>{});
+      if (i + 1 < nlive) pchunk(std::integral_constant<int, 1>{});
     }
   } else {
-  gload(c_begin);
-  lstore(0);
-  gload(c_begin + 1);
-  __syncthreads();
-  if constexpr (SIMPLE) {
-    // dealt-out schedule (see the forward kernel): 16 k-step units per chunk, fragments of 4 k-steps double-buffered
-    // and fetched two units ahead, LDS stores / table lookups / tile loads between the units
-    float fa[2][4][TM], fd[2][4][TN];
-    int ao[TM], dofs[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) { ao[i] = (lane >> 5) * BKT + wm * TM * 32 + (lane & 31) + i * 32; SEGSDE_OPAQUE(ao[i]); }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) { dofs[j] = BP * BKT + (lane >> 5) * BN + wn * TN * 32 + (lane & 31) + j * 32; SEGSDE_OPAQUE(dofs[j]); }
-    auto fread = [&](int buf, int g, int slot) {
-      const float* St = smem + buf * STAGE;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) fa[slot][u][i] = St[ao[i] + 2 * (4 * g + u) * BKT];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) fd[slot][u][j] = St[dofs[j] + 2 * (4 * g + u) * BN];
-      }
-    };
+    gload(c_begin);
+    lstore(0);
+    gload(c_begin + 1);
+    __syncthreads();
     for (int c = c_begin; c < c_end; ++c) {
       const int buf = (c - c_begin) & 1;
-      fread(buf, 0, 0);
-      tload();
-#pragma unroll
-      for (int u = 0; u < BP / 2; ++u) {
-        const int g = u / 4, st = u % 4;
-        if (st == 2 && g + 1 < BP / 8) fread(buf, g + 1, (g + 1) & 1);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][st][i], fd[g & 1][st][j], acc[i][j], 0, 0, 0);
-        if (u == 0) lstore(buf ^ 1);
-        if (u == 3) aload(c + 2);
-        if (u == 5) dload(c + 2);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      mma_steps(buf, 0, BP / 4);
+      lstore(buf ^ 1);
+      gload(c + 2);
+      mma_steps(buf, BP / 4, BP / 2);
       __syncthreads();
     }
-  } else
-  for (int c = c_begin; c < c_end; ++c) {
-    const int buf = (c - c_begin) & 1;
-    mma_steps(buf, 0, BP / 4);
-    lstore(buf ^ 1);
-    gload(c + 2);
-    mma_steps(buf, BP / 4, BP / 2);
-    __syncthreads();
-  }
   }
 
   float* out = part + (long)zt * p.Ktot * p.N;
@@ -1726,32 +1618,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
         if (k < p.Ktot) out[(long)k * p.N + n] = acc[i][j][r];
       }
   }
-  if (!wr.tickets) return;
-  // ---- last workgroup of this (k-tile, n-tile) reduces the splits
-  __threadfence();                                   // release: the slab is visible device-wide before the ticket is drawn
-  __syncthreads();
-  unsigned* flag = reinterpret_cast<unsigned*>(smem);
-  const int nsplit_z = (int)gridDim.x / (nkt * nnt);
-  if (tid == 0) flag[0] = atomicAdd(&wr.tickets[nt * nkt + kt], 1u) == (unsigned)(nsplit_z - 1) ? 1u : 0u;
-  __syncthreads();
-  if (!flag[0]) return;
-  __threadfence();                                   // acquire: the other workgroups' slabs
-  const long slab = (long)p.Ktot * p.N;
-  for (int e = tid; e < BKT * BN; e += 256) {
-    const int kl = e / BN, nl = e - kl * BN, k = k0 + kl, n = n0 + nl;
-    if (k >= p.Ktot || n >= p.N) continue;
-    const float* src = part + (long)k * p.N + n;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int z = 0;
-    for (; z + 3 < nsplit_z; z += 4) {
-      s0 += src[(long)z * slab]; s1 += src[(long)(z + 1) * slab]; s2 += src[(long)(z + 2) * slab]; s3 += src[(long)(z + 3) * slab];
-    }
-    for (; z < nsplit_z; ++z) s0 += src[(long)z * slab];
-    int tap, c;
-    wgrad_k_decode(k, p.Ctot, wr.taps, wr.srcC0, tap, c);
-    wr.dw[((long)n * wr.CtotDst + wr.cOff + c) * wr.taps + tap] = (s0 + s1) + (s2 + s3);
-  }
-  if (tid == 0) wr.tickets[nt * nkt + kt] = 0u;      // ready for the next launch that is handed this slice
 }
 
 // dW[o][c][kh][kw] (OIHW, the state_dict layout) = sum_z part[z][(kh*KW+kw)*Ctot + c][o], fixed order
@@ -1865,33 +1731,6 @@ __global__ __launch_bounds__(256) void reflect_dgrad_fix_kernel(const float* dy,
   }
 }
 
-// experiment knob (environment SEGSDE_TUNE="bk64=1"), read once.  Measured on MI355X (profiles/ab_conv_r01.log):
-// BK=64 (139 KB LDS => 1 workgroup/CU, half the barriers) loses 15-25 % on the large layers against BK=32 with two
-// co-resident workgroups per CU, and start-up staggering of co-resident workgroups changes nothing.
-struct Tune { int bk64 = 0; int adjfix = 0; int wplan = 0; int wovh = 4; int nos2 = 0; int dma = 1; int var = 0; int wdma = 2; int adjlds = 1; int wred = 0; int adjb = 1; int tskip = 1; int tsbn = 0; };
-const Tune& tune() {
-  static Tune t = [] {
-    Tune r;
-    if (const char* e = getenv("SEGSDE_TUNE")) {
-      if (const char* q = strstr(e, "bk64=")) r.bk64 = atoi(q + 5);
-      if (const char* q = strstr(e, "nos2=")) r.nos2 = atoi(q + 5);       // 1: stride-2 data-gradients without the parity split
-      if (const char* q = strstr(e, "wplan=")) r.wplan = atoi(q + 6);     // 1: previous fixed-target split plan
-      if (const char* q = strstr(e, "wovh=")) r.wovh = atoi(q + 5);       // per-workgroup fixed cost in chunk units
-      if (const char* q = strstr(e, "adjfix=")) r.adjfix = atoi(q + 7);   // reflection adjoint: plain loop + border fix-up kernel
-      if (const char* q = strstr(e, "dma=")) r.dma = atoi(q + 4);         // 0: register-staged tile loads (round-1 loop)
-      if (const char* q = strstr(e, "var=")) r.var = atoi(q + 4);         // experiment variants of the LDS-DMA loop
-      if (const char* q = strstr(e, "adjl=")) r.adjlds = atoi(q + 5);     // 0: reflection-adjoint loop register-staged in every wave
-      if (const char* q = strstr(e, "wlds=")) r.wdma = atoi(q + 5);       // 0: register-staged weight-gradient tile loads, 1: LDS-DMA with the barrier at the chunk end (round 2), 2: barrier inside the chunk (round 4)
-      if (const char* q = strstr(e, "adjb=")) r.adjb = atoi(q + 5);       // 0: reflection adjoint always inside the kernel (MODE 3); 1: zero-pad + border launches on the largest maps; 2: everywhere
-      if (const char* q = strstr(e, "tsbn=")) r.tsbn = atoi(q + 5);       // 1: 128x64 tiles for every one-round grid with dead tap rows, -1: for none (default 0: where the imbalance exceeds a fifth)
-      if (const char* q = strstr(e, "tskip=")) r.tskip = atoi(q + 6);     // 0: dilated zero-padded windows run their dead tap rows too
-      if (const char* q = strstr(e, "wred=")) r.wred = atoi(q + 5);       // 1: split partials reduced inside the kernel (measured: slower)
-    }
-    return r;
-  }();
-  return t;
-}
-
 // segsde_conv_compute_taken runs the entry points' own dispatch with this set: every implicit-GEMM launch reports the arithmetic
 // it would run in (launch_igemm / launch_wgrad, from the predicates they dispatch on) and nothing is launched
 struct ComputeProbe { int launches = 0, lo = 3, hi = 0; };
@@ -1954,18 +1793,12 @@ ConvP make_params(const segsde_conv_desc* d, const float* x0, const float* x1, c
   p.kh0 = 0; p.khs = 1; p.kw0 = 0; p.kws = 1; p.KWf = p.KW; p.Kfull = p.Ktot; p.os = 1; p.oph = 0; p.opw = 0; p.OHf = p.Ho; p.OWf = p.Wo;
   p.stats = nullptr;
   p.accum = d->accumulate ? 1 : 0;
-  {
-    // streaming stores for outputs far beyond the memory-side cache (SEGSDE_CONV_NT_MB: threshold in MiB, 0 = never; default off until measured)
-    static long nt_bytes = -1;
-    if (nt_bytes < 0) { const char* e = getenv("SEGSDE_CONV_NT_MB"); nt_bytes = (e ? atol(e) : 0L) << 20; }
-    p.nt = (nt_bytes > 0 && (long)p.M * p.N * 4 >= nt_bytes) ? 1 : 0;
-  }
   p.cmp = (d->compute == 1 || d->compute == 2) ? d->compute : 0;
   p.agy = nullptr; p.agld = 0; p.agkind = 0;
   p.lin = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->in_div <= 1 && !d->up0 && !d->sum2x2 && d->C1 == 0 &&
           d->H == d->Ho && d->W == d->Wo;
   p.padw = p.pad; p.wtap = p.Ctot; p.osfast = 0; p.submap = 0;
-  p.tapskip = (tune().tskip && d->pad_mode == SEGSDE_PAD_ZERO && d->dil > 1 && d->KH > 1 && d->in_div <= 1 && !d->up0 && !d->sum2x2 &&
+  p.tapskip = (d->pad_mode == SEGSDE_PAD_ZERO && d->dil > 1 && d->KH > 1 && d->in_div <= 1 && !d->up0 && !d->sum2x2 &&
                d->stride == 1) ? 1 : 0;
   p.wbstride = 0;
   return p;
@@ -2008,68 +1841,47 @@ bool igemm_fast_ok(const ConvP& p) {
   return fast_ok(p) && p.KH * p.KW <= 16 /* tap table in LDS */ && span * (i0 > i1 ? i0 : i1) < (1L << 31) &&
          (long)p.N * p.Ktot * 4 < (1L << 31);
 }
-bool bk64_ok(const ConvP& p) { return igemm_fast_ok(p) && (p.Ctot % 64 == 0) && (p.C1 == 0 || p.C0 % 64 == 0); }
 
-template <int BM, int BN, int WM, int WN, int MODE, int BK, int VAR = 0>
+template <int BM, int BN, int WM, int WN, int MODE, bool CLAMP = false, int CMP = 0>
 int launch_igemm_mode(const ConvP& p, hipStream_t stream) {
   const int nblk = segsde_cdiv(p.M, BM) * segsde_cdiv(p.ne - p.nb, BN);
-  size_t smem = (VAR == 4 ? 4 : 2) * (size_t)(BM + BN) * BK * sizeof(float);
+  size_t smem = 2 * (size_t)(BM + BN) * BK * sizeof(float);
   if (smem < (size_t)BM * BN * sizeof(float)) smem = (size_t)BM * BN * sizeof(float);   // the staged epilogue's tile
   if (MODE >= 2) smem += (size_t)(((MODE == 3 && BN >= 128) || p.C0 < p.Ctot) ? 2 : 1) * p.KH * p.KW * BM * sizeof(unsigned);   // tap table
-  auto k = conv_igemm_kernel<BM, BN, WM, WN, MODE, BK, VAR>;
+  auto k = conv_igemm_kernel<BM, BN, WM, WN, MODE, CLAMP, CMP>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   hipLaunchKernelGGL(k, dim3(nblk), dim3(256), smem, stream, p);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }
 
-// The arithmetic launch_igemm<.., BN, ..> runs p in: p.cmp where the launch takes the shipped LDS-DMA loop (MODE 4), else 0 -- the
-// in-kernel reflection adjoint (MODE 3), the experiment variants of SEGSDE_TUNE and the gathers have fp32 instantiations only.
-// launch_igemm dispatches on this value and segsde_conv_compute_taken reports it.
-template <int BN>
-int igemm_compute(const ConvP& p) {
-  if (!p.cmp || !igemm_fast_ok(p)) return 0;
-  if (p.pad_mode == SEGSDE_PAD_CLAMP_) return p.cmp;
-  if (p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && !(tune().adjfix && !p.sum2x2) && tune().adjfix < 2) return 0;
-  if ((tune().bk64 && bk64_ok(p)) || !tune().dma) return 0;
-  const int v = tune().var;
-  if (v == 1 || v == 2 || v == 3 || v == 7 || (v == 4 && BN >= 64) || (v == 6 && BN == 64)) return 0;
-  return p.cmp;
+// the reflection adjoint computed inside the kernel (MODE 3: bordered waves add the mirrored pre-images to their rows)
+bool igemm_adjoint_in_kernel(const ConvP& p) { return igemm_fast_ok(p) && p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT; }
+
+// The arithmetic launch_igemm runs p in: p.cmp where the launch takes the LDS-DMA loop (MODE 4), else 0 -- the in-kernel
+// reflection adjoint (MODE 3) and the gathers have fp32 instantiations only.  launch_igemm dispatches on this value and
+// segsde_conv_compute_taken reports it.
+int igemm_compute(const ConvP& p) { return (igemm_fast_ok(p) && !igemm_adjoint_in_kernel(p)) ? p.cmp : 0; }
+
+template <int BM, int BN, int WM, int WN, bool CLAMP>
+int launch_igemm_dma(const ConvP& p, int cmp, hipStream_t stream) {
+  return cmp == 1   ? launch_igemm_mode<BM, BN, WM, WN, 4, CLAMP, 1>(p, stream)
+         : cmp == 2 ? launch_igemm_mode<BM, BN, WM, WN, 4, CLAMP, 2>(p, stream)
+                    : launch_igemm_mode<BM, BN, WM, WN, 4, CLAMP, 0>(p, stream);
 }
 
 template <int BM, int BN, int WM, int WN>
 int launch_igemm(const ConvP& p, hipStream_t stream) {
-  const int cmp = igemm_compute<BN>(p);
+  const int cmp = igemm_compute(p);
   if (probing()) return probe_note(cmp);
-  if (cmp) {
-    if (p.pad_mode == SEGSDE_PAD_CLAMP_)   // upsample-folded class launches
-      return cmp == 1 ? launch_igemm_mode<BM, BN, WM, WN, 4, 32, 16 + 9>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 4, 32, 32 + 9>(p, stream);
-    return cmp == 1 ? launch_igemm_mode<BM, BN, WM, WN, 4, 32, 16>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 4, 32, 32>(p, stream);
-  }
-  if (igemm_fast_ok(p) && p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && !(tune().adjfix && !p.sum2x2) && tune().adjfix < 2)
-    return tune().var == 8 ? launch_igemm_mode<BM, BN, WM, WN, 3, 32, 8>(p, stream)
-           : (tune().adjlds ? launch_igemm_mode<BM, BN, WM, WN, 3, 32>(p, stream) : launch_igemm_mode<BM, BN, WM, WN, 3, 32, 5>(p, stream));
-  if (p.pad_mode == SEGSDE_PAD_CLAMP_) { // upsample-folded class launches (host guarantees the FAST conditions)
+  if (igemm_adjoint_in_kernel(p)) return launch_igemm_mode<BM, BN, WM, WN, 3>(p, stream);
+  if (p.pad_mode == SEGSDE_PAD_CLAMP_) {   // upsample-folded class launches (host guarantees the FAST conditions)
     if (!igemm_fast_ok(p)) return SEGSDE_ERR_UNSUPPORTED;
-    return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 9>(p, stream);
+    return launch_igemm_dma<BM, BN, WM, WN, true>(p, cmp, stream);
   }
-  if (tune().bk64 && bk64_ok(p)) return launch_igemm_mode<BM, BN, WM, WN, 2, 64>(p, stream);
-  if (igemm_fast_ok(p) && tune().dma) {
-    if (tune().var == 1) return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 1>(p, stream);
-    if (tune().var == 2) return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 2>(p, stream);
-    if (tune().var == 3) return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 3>(p, stream);
-    if constexpr (BN >= 64) {
-      if (tune().var == 4) return launch_igemm_mode<BM, BN, WM, WN, 4, 16, 4>(p, stream);
-    }
-    if (tune().var == 7) return launch_igemm_mode<BM, BN, WM, WN, 4, 32, 7>(p, stream);
-    if constexpr (BN == 64) {
-      if (tune().var == 6) return launch_igemm_mode<BM, BN, WM, WN, 4, 16, 6>(p, stream);
-    }
-    return launch_igemm_mode<BM, BN, WM, WN, 4, 32>(p, stream);
-  }
-  if (igemm_fast_ok(p)) return launch_igemm_mode<BM, BN, WM, WN, 2, 32>(p, stream);
-  if (vec_ok(p)) return launch_igemm_mode<BM, BN, WM, WN, 1, 32>(p, stream);
-  return launch_igemm_mode<BM, BN, WM, WN, 0, 32>(p, stream);
+  if (igemm_fast_ok(p)) return launch_igemm_dma<BM, BN, WM, WN, false>(p, cmp, stream);
+  if (vec_ok(p)) return launch_igemm_mode<BM, BN, WM, WN, 1>(p, stream);
+  return launch_igemm_mode<BM, BN, WM, WN, 0>(p, stream);
 }
 
 int launch_reflect_fix(const float* dy, int lddy, const float* wd, float* dx, int lddx, float* dx2, int lddx2, int nsplit,
@@ -2093,11 +1905,10 @@ namespace {
 // Round 4: it pays where the one-round grid loses more than a fifth to the imbalance -- mean live tap rows per output row
 // below 0.8 of the maximum (rate 12 on the 32-row map: 8 rows with three live tap rows, 24 with two -> 0.75; measured 4.13 ->
 // 3.80 ms/step) -- and costs where it does not (rate 6: 0.875, rate 18: 0.94: the 128x64 tile's lower rate is all that is left;
-// 4.16 -> 4.54 and 2.78 -> 3.12 ms/step, profiles/experiments_r03.md).  tsbn=1 forces it, tsbn=-1 turns it off.
+// 4.16 -> 4.54 and 2.78 -> 3.12 ms/step, profiles/experiments_r03.md).
 bool narrow_for_tapskip(const ConvP& q) {
-  if (!q.tapskip || tune().tsbn < 0 || q.N <= 64 || (q.ne - q.nb) % 64 != 0 ||
+  if (!q.tapskip || q.N <= 64 || (q.ne - q.nb) % 64 != 0 ||
       (long)segsde_cdiv(q.M, 128) * segsde_cdiv(q.ne - q.nb, 128) > 512) return false;
-  if (tune().tsbn > 0) return true;
   long live = 0; int most = 0;
   for (int h = 0; h < q.Ho; ++h) {
     int n = 0;
@@ -2192,10 +2003,10 @@ int launch_adjoint_by_borders(const ConvP& p, hipStream_t s, bool with_main = tr
 }
 bool adjoint_by_borders_ok(const ConvP& p) {
   // measured (profiles/experiments_r03.md): the five extra launches cost ~70 us per call -- a gain only on the largest maps
-  // (128 -> 64 @256x512 x 16: 5.63 -> 5.46 ms/step), a loss below (256 -> 256 @32x64: 0.69 -> 1.15); adjb=2 forces it everywhere
+  // (128 -> 64 @256x512 x 16: 5.63 -> 5.46 ms/step), a loss below (256 -> 256 @32x64: 0.69 -> 1.15)
   // (half-precision / split-bf16 operand modes: always -- the in-kernel adjoint, MODE 3, has fp32 instantiations only)
-  const bool big = (long)p.B * p.H * p.W >= (1L << 21) || tune().adjb == 2 || p.cmp;
-  return tune().adjb && big && p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && igemm_fast_ok(p) && !p.sum2x2 && p.vecout && p.H >= 4 &&
+  const bool big = (long)p.B * p.H * p.W >= (1L << 21) || p.cmp;
+  return big && p.pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && igemm_fast_ok(p) && !p.sum2x2 && p.vecout && p.H >= 4 &&
          p.W >= 4 && p.C1 == 0 && p.KH == 3 && p.KW == 3 && p.nb == 0 && p.ne == p.N;
 }
 }  // namespace
@@ -2273,7 +2084,7 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
   }
   // data-gradient of a stride-2 convolution as four parity classes (below): what an accumulating launch needs from it
   const bool parity_split = d->in_div == 2 && d->stride == 1 && (d->dil & 1) && d->pad_mode == SEGSDE_PAD_ZERO && !d->sum2x2 &&
-                            d->C1 == 0 && !d->up0 && !bias && d->act == 0 && !y2 && !tune().nos2 && p.vecout;
+                            d->C1 == 0 && !d->up0 && !bias && d->act == 0 && !y2 && p.vecout;
   if (d->accumulate) {
     // only the plain staged-epilogue launches add in place: one destination, no activation / bias, no special route
     // (round 4: and the parity classes of a stride-2 data-gradient, whose sub-grid stores add just the same)
@@ -2347,7 +2158,7 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
   }
   // shapes whose mirrored-padding contributions are added by a second kernel (below) cannot have the activation derivative
   // applied in the first kernel's epilogue: the caller runs the separate pass
-  if (p.agy && d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && (!igemm_fast_ok(p) || (tune().adjfix && !p.sum2x2)))
+  if (p.agy && d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && !igemm_fast_ok(p))
     return SEGSDE_ERR_UNSUPPORTED;
   if (d->sum2x2) {
     if ((d->Ho & 1) || (d->Wo & 1) || d->stride != 1 || d->act != 0 || bias) return SEGSDE_ERR_SHAPE;
@@ -2360,69 +2171,56 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
   // tile width by N: 32 / 64 for narrow outputs (a 256x64 tile measured 3 % slower), 128-wide tiles for the bulk and 64-wide
   // ones for a 64-channel tail (e.g. the 192-channel concat data-gradient)
   if (int e = launch_by_n(p, s)) return e;
-  if (d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && (!igemm_fast_ok(p) || (tune().adjfix && !p.sum2x2)))
+  if (d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT && !igemm_fast_ok(p))
     // the generic gathers treat the padding as zeros; add the mirrored-padding contributions on the border pixels
     return launch_reflect_fix(x0, p.ld0, wpack, y, p.ldy, y2, p.ldy2, p.nsplit, p.B, p.H, p.W, p.N, p.C0, s);
   return 0;
 }
 
 namespace {
-template <int BKT, int BN, int WM, int WN, int MODEX>
-int launch_wgrad_mode(const ConvP& p, const float* dy, int lddy, float* ws, int splits, int cps, hipStream_t stream, WRed wr) {
-  constexpr int MODE = MODEX & 15;
+template <int BKT, int BN, int WM, int WN, int MODE, int CMP = 0>
+int launch_wgrad_mode(const ConvP& p, const float* dy, int lddy, float* ws, int splits, int cps, hipStream_t stream) {
   const dim3 grid(segsde_cdiv(p.Ktot, BKT) * segsde_cdiv(p.N, BN) * splits);
   size_t smem = 2 * (size_t)BP * (BKT + BN) * sizeof(float);
-  if (MODE == 2 || MODE == 4 || MODE == 5)   // + the four offset tables (padded rows / columns of the two sources)
+  if (MODE == 5)   // + the four offset tables (padded rows / columns of the two sources)
     smem += 2 * (size_t)((p.Ho - 1) * p.stride + (p.KH - 1) * p.dil + 1 + (p.Wo - 1) * p.stride + (p.KW - 1) * p.dil + 1) * sizeof(unsigned);
-  auto k = conv_wgrad_kernel<BKT, BN, WM, WN, MODEX>;
+  auto k = conv_wgrad_kernel<BKT, BN, WM, WN, MODE, CMP>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(k, grid, dim3(256), smem, stream, p, dy, lddy, ws, cps, wr);
+  hipLaunchKernelGGL(k, grid, dim3(256), smem, stream, p, dy, lddy, ws, cps);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }
 
-// 2: table-driven loader (rows a multiple of 32 pixels wide), 3: general fast gather, 1: float4 gather, 0: scalar gather
+// conv_wgrad_kernel's MODE for p: 5 table-driven LDS-DMA loader (rows a multiple of 32 pixels wide), 3: general fast gather,
+// 1: float4 gather, 0: scalar gather
 int wgrad_mode(const ConvP& p, const float* dy, int lddy) {
   const bool vec = vec_ok(p) && (p.N % 4 == 0) && (lddy % 4 == 0) && aligned16(dy);
   const long e0 = (long)p.B * (p.H >> p.up0) * (p.W >> p.up0) * p.ld0, e1 = (long)p.B * p.H * p.W * p.ld1;
   const bool fast = vec_ok(p) && e0 < (1L << 31) && e1 < (1L << 31);   // the dY side may be scalar (odd Cout)
   const long i0 = (long)(p.H >> p.up0) * (p.W >> p.up0) * p.ld0 * 4, i1 = (long)p.H * p.W * p.ld1 * 4;
   const bool table = p.Wo % BP == 0 && i0 <= (1L << 30) && i1 <= (1L << 30) && (long)BP * p.os * lddy * 4 < (1L << 30);
-  if (fast && vec && table) return 2;
+  if (fast && vec && table) return 5;
   if (fast) return 3;
   return vec ? 1 : 0;
 }
 
 // The arithmetic launch_wgrad runs p in: p.cmp on the pipelined LDS-DMA loop (MODE 5), else 0 (the other loops are fp32 only).
 // launch_wgrad dispatches on this value and segsde_conv_compute_taken reports it.
-int wgrad_compute(const ConvP& p, const float* dy, int lddy) {
-  return (p.cmp && wgrad_mode(p, dy, lddy) == 2 && tune().wdma == 2) ? p.cmp : 0;
-}
+int wgrad_compute(const ConvP& p, const float* dy, int lddy) { return wgrad_mode(p, dy, lddy) == 5 ? p.cmp : 0; }
 
 template <int BKT, int BN, int WM, int WN>
-int launch_wgrad(const ConvP& p, const float* dy, int lddy, float* ws, int splits, int cps, hipStream_t stream, WRed wr = WRed{}) {
+int launch_wgrad(const ConvP& p, const float* dy, int lddy, float* ws, int splits, int cps, hipStream_t stream) {
   const int cmp = wgrad_compute(p, dy, lddy);
   if (probing()) return probe_note(cmp);
-  if (cmp)
-    return cmp == 1 ? launch_wgrad_mode<BKT, BN, WM, WN, 16 + 5>(p, dy, lddy, ws, splits, cps, stream, wr)
-                    : launch_wgrad_mode<BKT, BN, WM, WN, 32 + 5>(p, dy, lddy, ws, splits, cps, stream, wr);
   switch (wgrad_mode(p, dy, lddy)) {
-    case 2:
-      if (tune().wdma == 2) return launch_wgrad_mode<BKT, BN, WM, WN, 5>(p, dy, lddy, ws, splits, cps, stream, wr);
-      if (tune().wdma) return launch_wgrad_mode<BKT, BN, WM, WN, 4>(p, dy, lddy, ws, splits, cps, stream, wr);
-      return launch_wgrad_mode<BKT, BN, WM, WN, 2>(p, dy, lddy, ws, splits, cps, stream, wr);
-    case 3: return launch_wgrad_mode<BKT, BN, WM, WN, 3>(p, dy, lddy, ws, splits, cps, stream, wr);
-    case 1: return launch_wgrad_mode<BKT, BN, WM, WN, 1>(p, dy, lddy, ws, splits, cps, stream, wr);
-    default: return launch_wgrad_mode<BKT, BN, WM, WN, 0>(p, dy, lddy, ws, splits, cps, stream, wr);
+    case 5:
+      return cmp == 1   ? launch_wgrad_mode<BKT, BN, WM, WN, 5, 1>(p, dy, lddy, ws, splits, cps, stream)
+             : cmp == 2 ? launch_wgrad_mode<BKT, BN, WM, WN, 5, 2>(p, dy, lddy, ws, splits, cps, stream)
+                        : launch_wgrad_mode<BKT, BN, WM, WN, 5, 0>(p, dy, lddy, ws, splits, cps, stream);
+    case 3: return launch_wgrad_mode<BKT, BN, WM, WN, 3>(p, dy, lddy, ws, splits, cps, stream);
+    case 1: return launch_wgrad_mode<BKT, BN, WM, WN, 1>(p, dy, lddy, ws, splits, cps, stream);
+    default: return launch_wgrad_mode<BKT, BN, WM, WN, 0>(p, dy, lddy, ws, splits, cps, stream);
   }
-}
-
-WRed make_wred(const ConvP& p, int bkt, int bn, float* dw, int CtotDst, int cOff, int taps, int srcC0) {
-  WRed wr{};
-  if (!tune().wred || probing()) return wr;
-  wr.tickets = segsde_ticket_slice(segsde_cdiv(p.Ktot, bkt) * segsde_cdiv(p.N, bn));
-  wr.dw = dw; wr.CtotDst = CtotDst; wr.cOff = cOff; wr.taps = taps; wr.srcC0 = srcC0;
-  return wr;
 }
 
 void wgrad_plan(const segsde_conv_desc* d, int& bkt, int& bn, int& splits, int& cps) {
@@ -2432,30 +2230,21 @@ void wgrad_plan(const segsde_conv_desc* d, int& bkt, int& bn, int& splits, int& 
   bkt = 128;
   const long tiles = (long)segsde_cdiv(Ktot, bkt) * segsde_cdiv(d->Cout, bn);
   const int nchunks = segsde_cdiv(M, BP);
-  long want;
-  if (tune().wplan == 0) {
-    // Equal-sized workgroups run in waves of `slots` (2 per CU for the 128x128 tile, 3 for the narrower ones): a split
-    // count that puts a handful of workgroups into one more wave costs a whole extra pass.  Pick the split count that
-    // minimises waves x (chunks per split + fixed per-workgroup cost), preferring fewer splits on ties.
-    const long slots = 256L * (bn == 128 ? 2 : 3);
-    const long ovh = tune().wovh;
-    long best = -1, best_cost = 0;
-    const long smax = nchunks / 8 > 1 ? (nchunks / 8 < 1024 ? nchunks / 8 : 1024) : 1;
-    for (long sp = 1; sp <= smax; ++sp) {
-      const long c = (nchunks + sp - 1) / sp, se = (nchunks + c - 1) / c;
-      const long waves = (tiles * se + slots - 1) / slots;
-      const long cost = waves * (c + ovh);
-      if (best < 0 || cost < best_cost) { best = se; best_cost = cost; }
-    }
-    want = best;
-  } else {
-    want = (1536 + tiles - 1) / tiles;          // ~6 workgroups per CU overall (2 resident): measured best for long loops
-    if (nchunks / want < 64) {                       // short reductions: fewer, longer splits amortise prologue/epilogue
-      want = (1024 + tiles - 1) / tiles;
-      if (want > nchunks / 8) want = nchunks / 8;
-    }
+  // Equal-sized workgroups run in waves of `slots` (2 per CU for the 128x128 tile, 3 for the narrower ones): a split
+  // count that puts a handful of workgroups into one more wave costs a whole extra pass.  Pick the split count that
+  // minimises waves x (chunks per split + fixed per-workgroup cost), preferring fewer splits on ties.  (Replaced a fixed
+  // target of ~6 workgroups per CU, profiles/experiments_r01.md.)
+  const long slots = 256L * (bn == 128 ? 2 : 3);
+  constexpr long WG_OVERHEAD_CHUNKS = 4;   // fixed per-workgroup cost (prologue, epilogue, partial slab) in chunk units
+  long best = -1, best_cost = 0;
+  const long smax = nchunks / 8 > 1 ? (nchunks / 8 < 1024 ? nchunks / 8 : 1024) : 1;
+  for (long sp = 1; sp <= smax; ++sp) {
+    const long c = (nchunks + sp - 1) / sp, se = (nchunks + c - 1) / c;
+    const long waves = (tiles * se + slots - 1) / slots;
+    const long cost = waves * (c + WG_OVERHEAD_CHUNKS);
+    if (best < 0 || cost < best_cost) { best = se; best_cost = cost; }
   }
-  cps = segsde_cdiv(nchunks, want);
+  cps = segsde_cdiv(nchunks, best);
   splits = segsde_cdiv(nchunks, cps);
 }
 }  // namespace
@@ -2488,16 +2277,14 @@ extern "C" int segsde_conv2d_wgrad(const segsde_conv_desc* d, const float* x0, c
   int bkt, bn, splits, cps;
   wgrad_plan(d, bkt, bn, splits, cps);
   int e;
-  const int srcmaj = (wgrad_mode(p, dy, lddy) == 2 && p.C1 > 0) ? p.C0 : 0;
-  const WRed wr = make_wred(p, bkt, bn, dw_oihw, p.Ctot, 0, d->KH * d->KW, srcmaj);
-  if (bn == 32) e = launch_wgrad<128, 32, 4, 1>(p, dy, lddy, workspace, splits, cps, s, wr);
-  else if (bn == 64) e = launch_wgrad<128, 64, 2, 2>(p, dy, lddy, workspace, splits, cps, s, wr);
-  else e = launch_wgrad<128, 128, 2, 2>(p, dy, lddy, workspace, splits, cps, s, wr);
+  if (bn == 32) e = launch_wgrad<128, 32, 4, 1>(p, dy, lddy, workspace, splits, cps, s);
+  else if (bn == 64) e = launch_wgrad<128, 64, 2, 2>(p, dy, lddy, workspace, splits, cps, s);
+  else e = launch_wgrad<128, 128, 2, 2>(p, dy, lddy, workspace, splits, cps, s);
   if (e) return e;
-  if (wr.tickets || probing()) return 0;
+  if (probing()) return 0;
   const long total = (long)p.Ktot * p.N;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, workspace, splits,
-                     p.Ktot, p.N, p.Ctot, d->KH * d->KW, (wgrad_mode(p, dy, lddy) == 2 && p.C1 > 0) ? p.C0 : 0, dw_oihw, p.Ctot, 0);
+                     p.Ktot, p.N, p.Ctot, d->KH * d->KW, (wgrad_mode(p, dy, lddy) == 5 && p.C1 > 0) ? p.C0 : 0, dw_oihw, p.Ctot, 0);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }
@@ -2841,7 +2628,7 @@ extern "C" int segsde_conv2d_wgrad_upfold(const segsde_conv_desc* d, const float
     ConvP q = make_params(&c, x0, nullptr, dy, nullptr, workspace + k * slab, nullptr);
     q.pad_mode = SEGSDE_PAD_CLAMP_; q.padw = 1 - px;
     q.os = 2; q.oph = py; q.opw = px; q.OHf = d->H; q.OWf = d->W;
-    if (wgrad_mode(q, dy, lddy) != 2) return SEGSDE_ERR_UNSUPPORTED;   // the table-driven loader is the one that knows sub-grids
+    if (wgrad_mode(q, dy, lddy) != 5) return SEGSDE_ERR_UNSUPPORTED;   // the table-driven loader is the one that knows sub-grids
     cls[k] = q;
   }
   ConvP r;
@@ -2849,7 +2636,7 @@ extern "C" int segsde_conv2d_wgrad_upfold(const segsde_conv_desc* d, const float
     r = make_params(&pl.skip, x1, nullptr, dy, nullptr, workspace + 4 * slab, nullptr);
   }
   for (int k = 0; k < 4; ++k)
-    if (int e = launch_wgrad_by_bn(pl.bn, cls[k], dy, lddy, workspace + k * slab, pl.splits, pl.cps, s, WRed{})) return e;
+    if (int e = launch_wgrad_by_bn(pl.bn, cls[k], dy, lddy, workspace + k * slab, pl.splits, pl.cps, s)) return e;
   if (!probing()) {
     const long total = (long)d->Cout * d->C0 * 9;
     hipLaunchKernelGGL(upfold_wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, workspace, pl.splits,
@@ -2858,9 +2645,8 @@ extern "C" int segsde_conv2d_wgrad_upfold(const segsde_conv_desc* d, const float
   }
   if (d->C1) {
     float* ws1 = workspace + 4 * slab;
-    const WRed wr = make_wred(r, 128, pl.bn1, dw_oihw, Ctot, d->C0, 9, 0);
-    if (int e = launch_wgrad_by_bn(pl.bn1, r, dy, lddy, ws1, pl.splits1, pl.cps1, s, wr)) return e;
-    if (wr.tickets || probing()) return 0;
+    if (int e = launch_wgrad_by_bn(pl.bn1, r, dy, lddy, ws1, pl.splits1, pl.cps1, s)) return e;
+    if (probing()) return 0;
     const long total = (long)r.Ktot * r.N;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, ws1, pl.splits1, r.Ktot, r.N, r.Ctot, 9, 0,
                        dw_oihw, Ctot, d->C0);
@@ -3022,14 +2808,14 @@ extern "C" int segsde_stem7x7_wgrad(const float* xpad, int B, int Hp, int Wp, in
   hipStream_t s = static_cast<hipStream_t>(stream);
   ConvP p = make_params(&c, xpad, nullptr, dy, nullptr, workspace, nullptr);
   const int mode = wgrad_mode(p, dy, lddy);
-  if (mode != 2 && mode != 3) return SEGSDE_ERR_UNSUPPORTED;
+  if (mode != 5 && mode != 3) return SEGSDE_ERR_UNSUPPORTED;
   int bkt, bn, splits, cps;
   wgrad_plan(&c, bkt, bn, splits, cps);
-  if (int e = launch_wgrad_by_bn(bn, p, dy, lddy, workspace, splits, cps, s, WRed{})) return e;
+  if (int e = launch_wgrad_by_bn(bn, p, dy, lddy, workspace, splits, cps, s)) return e;
   float* dwp = workspace + (size_t)splits * p.Ktot * p.N;
   const long total = (long)p.Ktot * p.N;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(segsde_cdiv(total, 32)), dim3(256), 1024, s, workspace, splits, p.Ktot, p.N, p.Ctot, 7,
-                     (mode == 2 && p.C1 > 0) ? p.C0 : 0, dwp, p.Ctot, 0);
+                     (mode == 5 && p.C1 > 0) ? p.C0 : 0, dwp, p.Ctot, 0);
   SEGSDE_CHECK_LAUNCH();
   hipLaunchKernelGGL(stem_unpack_kernel, dim3(segsde_cdiv((long)Cout * C * 49, 256)), dim3(256), 0, s, dwp, Cout, C, cp, dw_oihw);
   SEGSDE_CHECK_LAUNCH();
@@ -3140,7 +2926,7 @@ bool winograd_shape_ok(const segsde_conv_desc* d) {
          !d->accumulate && (d->pad_mode == SEGSDE_PAD_ZERO || (d->pad_mode == SEGSDE_PAD_REFLECT && d->dil == 1)) && d->H == d->Ho &&
          d->W == d->Wo && d->H % (2 * d->dil) == 0 && d->W % (2 * d->dil) == 0 && d->H >= 4 * d->dil && d->W >= 4 * d->dil &&
          C % 32 == 0 && d->C0 % 4 == 0 && d->Cout % 64 == 0 && d->ld0 % 4 == 0 && (!d->C1 || d->ld1 % 4 == 0) && d->ldy % 4 == 0 &&
-         16 * segsde_wino_rows(T) * (long)(C > d->Cout ? C : d->Cout) < (1L << 31) && tune().dma;
+         16 * segsde_wino_rows(T) * (long)(C > d->Cout ? C : d->Cout) < (1L << 31);
 }
 segsde_conv_desc winograd_gemm_desc(const segsde_conv_desc* d) {
   segsde_conv_desc g = *d;
@@ -3253,7 +3039,7 @@ extern "C" int segsde_conv2d_wgrad_winograd(const segsde_conv_desc* d, const flo
   float* dM = reinterpret_cast<float*>(base + pl.off_dm);
   float* part = reinterpret_cast<float*>(base + pl.off_part);
   ConvP p = make_params(&pl.g, V, nullptr, dM, nullptr, part, nullptr);
-  if (wgrad_mode(p, dM, d->Cout) != 2) return SEGSDE_ERR_UNSUPPORTED;
+  if (wgrad_mode(p, dM, d->Cout) != 5) return SEGSDE_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!v_saved)
     if (int e = segsde_wino_input(x0, d->ld0, d->C1 ? x1 : nullptr, d->C1 ? d->ld1 : d->ld0, d->C0, d->B, d->H, d->W, C, d->dil,

@@ -47,13 +47,12 @@ template <class Op, int VW, class = void> struct has_ctx : std::false_type {};
 template <class Op, int VW>
 struct has_ctx<Op, VW, std::void_t<decltype(std::declval<const Op&>().template ctx<VW>(0))>> : std::true_type {};
 
-// Fin: finalize inside the reduction kernel (round-3 EXPERIMENT, off by default -- see launch_colreduce).  The
-// block that draws the LAST ticket of its channel group folds the group's partial rows -- in the same fixed lane order as
-// pair_finalize_kernel, so the result is bit-identical to the two-kernel path -- and writes the float sums.
-struct Fin { unsigned* tickets; float* out0; float* out1; };
+// The partial rows are folded by a separate finalize kernel (pair_finalize_kernel, bn_stats_finalize_kernel), not by the last block
+// of each channel group: the device-scope fence that needs costs more than the ~7 us launch it replaces (colreduce<BnBwdOp>
+// 53 -> 222 us per launch on the 8-XCD part; profiles/experiments_r03.md).
 
 template <class Op, int VW, int TX>
-__global__ __launch_bounds__(256) void colreduce_kernel(Op op, long M, int C, double* part, Fin fin) {
+__global__ __launch_bounds__(256) void colreduce_kernel(Op op, long M, int C, double* part) {
   constexpr int TY = 256 / TX, CW = TX * VW;          // channels per block
   SEGSDE_SMEM;
   double* sh = reinterpret_cast<double*>(segsde_smem);  // [2][TY][CW]
@@ -91,67 +90,28 @@ __global__ __launch_bounds__(256) void colreduce_kernel(Op op, long M, int C, do
     part[((long)blockIdx.x * 2 + 0) * C + blockIdx.y * CW + cc] = a;
     part[((long)blockIdx.x * 2 + 1) * C + blockIdx.y * CW + cc] = b2;
   }
-  if (!fin.tickets) return;
-  __threadfence();
-  __syncthreads();
-  unsigned* flag = reinterpret_cast<unsigned*>(sh);
-  if (threadIdx.x == 0) flag[0] = atomicAdd(&fin.tickets[blockIdx.y], 1u) == (unsigned)(nb - 1) ? 1u : 0u;
-  __syncthreads();
-  const bool last = flag[0] != 0u;
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  // pair_finalize_kernel's order: 16 partial-lanes (lane l takes rows l, l + 16, ...), then lanes 0..15 in sequence
-  for (int t = threadIdx.x; t < 16 * CW; t += 256) {
-    const int l = t / CW, ch = t - l * CW, cg = blockIdx.y * CW + ch;
-    double a = 0.0, b2 = 0.0;
-    if (cg < C)
-      for (int i = l; i < nb; i += 16) { a += part[((long)i * 2) * C + cg]; b2 += part[((long)i * 2 + 1) * C + cg]; }
-    sh[l * CW + ch] = a; sh[(16 + l) * CW + ch] = b2;
-  }
-  __syncthreads();
-  if (cc < CW && blockIdx.y * CW + cc < C) {
-    double a = 0.0, b2 = 0.0;
-    for (int j = 0; j < 16; ++j) { a += sh[j * CW + cc]; b2 += sh[(16 + j) * CW + cc]; }
-    if (fin.out0) fin.out0[blockIdx.y * CW + cc] = (float)a;
-    if (fin.out1) fin.out1[blockIdx.y * CW + cc] = (float)b2;
-  }
-  if (threadIdx.x == 0) fin.tickets[blockIdx.y] = 0u;
 }
 
 template <class Op, int TX>
-void launch_colreduce_scalar(Op op, long M, int C, double* part, hipStream_t s, Fin fin) {
+void launch_colreduce_scalar(Op op, long M, int C, double* part, hipStream_t s) {
   const dim3 grid(red_blocks(M), (C + TX - 1) / TX);
-  // LDS: [2][TY][TX] block partials, and [2][16][TX] lane sums of the in-kernel finalize
-  const size_t smem = 2 * (size_t)(256 > 16 * TX ? 256 : 16 * TX) * sizeof(double);
-  hipLaunchKernelGGL((colreduce_kernel<Op, 1, TX>), grid, dim3(256), smem, s, op, M, C, part, fin);
+  const size_t smem = 2 * 256 * sizeof(double);   // [2][TY][TX] block partials
+  hipLaunchKernelGGL((colreduce_kernel<Op, 1, TX>), grid, dim3(256), smem, s, op, M, C, part);
 }
 
-// fin: out0 / out1 (nullable) receive the two column sums as floats from the reduction kernel itself (its last block per
-// channel group); returns true in *done when it did (the caller then skips pair_finalize_kernel)
 template <class Op>
-int launch_colreduce(Op op, long M, int C, double* part, bool vec, hipStream_t s, float* out0 = nullptr, float* out1 = nullptr,
-                     bool* done = nullptr) {
-  Fin fin{nullptr, out0, out1};
-  // off by default (SEGSDE_TUNE="cfin=1"): the device-scope fence costs more than the ~7 us finalize launch it replaces
-  // (colreduce<BnBwdOp> 53 -> 222 us per launch on the 8-XCD part; profiles/experiments_r03.md)
-  static const bool enabled = [] { const char* e = getenv("SEGSDE_TUNE"); return e && strstr(e, "cfin=1"); }();
-  if (done && enabled && (out0 || out1)) {
-    const int cw = vec ? SLAB : (C <= 1 ? 1 : C <= 2 ? 2 : C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : C <= 32 ? 32 : 64);   // channels per block
-    fin.tickets = segsde_ticket_slice((C + cw - 1) / cw);             // one ticket per channel group (grid.y)
-  }
+int launch_colreduce(Op op, long M, int C, double* part, bool vec, hipStream_t s) {
   if (vec) {
     const dim3 grid(red_blocks(M), (C + SLAB - 1) / SLAB);
-    hipLaunchKernelGGL((colreduce_kernel<Op, 4, SLAB / 4>), grid, dim3(256), 2 * 16 * SLAB * sizeof(double), s, op, M, C, part, fin);
-  } else if (C <= 1) launch_colreduce_scalar<Op, 1>(op, M, C, part, s, fin);
-  else if (C <= 2) launch_colreduce_scalar<Op, 2>(op, M, C, part, s, fin);
-  else if (C <= 4) launch_colreduce_scalar<Op, 4>(op, M, C, part, s, fin);
-  else if (C <= 8) launch_colreduce_scalar<Op, 8>(op, M, C, part, s, fin);
-  else if (C <= 16) launch_colreduce_scalar<Op, 16>(op, M, C, part, s, fin);
-  else if (C <= 32) launch_colreduce_scalar<Op, 32>(op, M, C, part, s, fin);
-  else launch_colreduce_scalar<Op, 64>(op, M, C, part, s, fin);
+    hipLaunchKernelGGL((colreduce_kernel<Op, 4, SLAB / 4>), grid, dim3(256), 2 * 16 * SLAB * sizeof(double), s, op, M, C, part);
+  } else if (C <= 1) launch_colreduce_scalar<Op, 1>(op, M, C, part, s);
+  else if (C <= 2) launch_colreduce_scalar<Op, 2>(op, M, C, part, s);
+  else if (C <= 4) launch_colreduce_scalar<Op, 4>(op, M, C, part, s);
+  else if (C <= 8) launch_colreduce_scalar<Op, 8>(op, M, C, part, s);
+  else if (C <= 16) launch_colreduce_scalar<Op, 16>(op, M, C, part, s);
+  else if (C <= 32) launch_colreduce_scalar<Op, 32>(op, M, C, part, s);
+  else launch_colreduce_scalar<Op, 64>(op, M, C, part, s);
   SEGSDE_CHECK_LAUNCH();
-  if (done) *done = fin.tickets != nullptr;
   return 0;
 }
 
@@ -994,13 +954,10 @@ extern "C" int segsde_bn_backward(const float* dy, int lddy, const float* y, int
   BnBwdOp op{dy, lddy, y, ldy, x, ldx, mean, invstd, act, C, drop_p, seed, gamma, beta};
   const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (lddy % 4 == 0) && al16p(x) && (!y || al16p(y)) && al16p(dy) &&
                    (!gamma || (al16p(gamma) && (!beta || al16p(beta)))) && al16p(mean) && al16p(invstd);
-  bool fin = false;
-  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream), dgamma, dbeta, &fin)) return e;
-  if (!fin) {
-    hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws,
-                       red_blocks(M), C, dgamma, dbeta);
-    SEGSDE_CHECK_LAUNCH();
-  }
+  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream))) return e;
+  hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws,
+                     red_blocks(M), C, dgamma, dbeta);
+  SEGSDE_CHECK_LAUNCH();
   if (dx || dres) {
     // (dgamma / dbeta may be slices of a gradient bucket: ddp.py aligns them, callers of the C ABI need not)
     const bool v4 = vec && (!dx || ((lddx % 4 == 0) && al16p(dx))) && (!dres || ((lddres % 4 == 0) && al16p(dres))) &&
@@ -1026,9 +983,8 @@ extern "C" int segsde_act_backward(const float* dy, int lddy, const float* y, in
   ActBwdOp op{dy, lddy, y, ldy, dz, lddz, act};
   const bool vec = (C % 4 == 0) && (ldy % 4 == 0) && (lddy % 4 == 0) && al16p(y) && al16p(dy) &&
                    (!dz || ((lddz % 4 == 0) && al16p(dz)));
-  bool fin = false;
-  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream), dbias, nullptr, &fin)) return e;
-  if (dbias && !fin) {
+  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream))) return e;
+  if (dbias) {
     hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws,
                        red_blocks(M), C, dbias, (float*)nullptr);
     SEGSDE_CHECK_LAUNCH();
@@ -1042,13 +998,10 @@ extern "C" int segsde_colsum(const float* x, int ldx, long M, int C, float* out,
   if (ws_bytes < part_bytes(M, C)) return SEGSDE_ERR_WORKSPACE;
   ColsumOp op{x, ldx};
   const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && al16p(x);
-  bool fin = false;
-  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream), out, nullptr, &fin)) return e;
-  if (!fin) {
-    hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws,
-                       red_blocks(M), C, out, (float*)nullptr);
-    SEGSDE_CHECK_LAUNCH();
-  }
+  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream))) return e;
+  hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws,
+                     red_blocks(M), C, out, (float*)nullptr);
+  SEGSDE_CHECK_LAUNCH();
   return 0;
 }
 

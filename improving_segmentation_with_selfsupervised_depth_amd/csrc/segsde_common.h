@@ -129,13 +129,6 @@ __device__ __forceinline__ void segsde_buffer_store4(segsde_rsrc r, unsigned vof
   d.x = __float_as_uint(v.x); d.y = __float_as_uint(v.y); d.z = __float_as_uint(v.z); d.w = __float_as_uint(v.w);
   __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, 0);   // out-of-range voff: the store is dropped
 }
-// the same store with the non-temporal ("nt": streaming) cache policy -- for outputs no cache level can hold until they are read
-__device__ __forceinline__ void segsde_buffer_store4_nt(segsde_rsrc r, unsigned voff, unsigned soff, float4 v) {
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  u32x4_t d;
-  d.x = __float_as_uint(v.x); d.y = __float_as_uint(v.y); d.z = __float_as_uint(v.z); d.w = __float_as_uint(v.w);
-  __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, 2);
-}
 // one dword per lane: with the lane's constant offset in the VGPR and everything wave-uniform in the SGPR offset a store / load of a
 // row of pixels costs no vector address arithmetic (the Winograd epilogue: 32 stores per thread)
 __device__ __forceinline__ void segsde_buffer_store1(segsde_rsrc r, unsigned voff, unsigned soff, float v) {
@@ -166,8 +159,6 @@ __device__ __forceinline__ void segsde_buffer_load4_lds(segsde_rsrc r, unsigned 
 // v_add_u32 to rebase -- vector issue slots taken from the matrix pipe in an MFMA loop.  Waits are still the compiler's.
 #define SEGSDE_LDS_READ_IMM(p, i) (((const volatile __attribute__((address_space(3))) float*)(p))[i])
 __device__ __forceinline__ void segsde_wait_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// at most N of this wave's vector-memory operations still outstanding (N tile loads of later chunks may stay in flight)
-template <int N> __device__ __forceinline__ void segsde_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 #endif
 
 // A fresh copy of the kernel's FIRST by-value argument, loaded from the kernel-argument segment at this point of the
@@ -200,11 +191,6 @@ __device__ __forceinline__ T segsde_kernarg_here() {
   } while (0)
 
 static inline int segsde_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
-// Tickets for "the last workgroup finishes the job" reductions (weight-gradient splits, column-sum finalize): a zeroed slice
-// of a device-resident ring for one launch (csrc/abi.hip); nullptr if it cannot be provided (the caller then uses its
-// two-kernel path).
-unsigned* segsde_ticket_slice(int n);
 
 // activation codes shared by conv epilogues, bn_apply and act_backward
 __device__ __forceinline__ float segsde_act(float v, int act) {

@@ -476,7 +476,7 @@ def _live_tap_frac(g, H, W, wgrad=False):
     for a whole 128-pixel tile (forward / data-gradient) or a whole output row (weight gradient, 128-column reduction tiles
     inside one tap row) are not multiplied.  Mirrors the kernels' tile-uniform rule for the reported 'executed' FLOPs; 1.0
     where the rule does not apply."""
-    if g.reflect or g.dil <= 1 or g.k <= 1 or g.stride != 1 or g.up0 or os.environ.get("SEGSDE_TUNE", "").find("tskip=0") >= 0:
+    if g.reflect or g.dil <= 1 or g.k <= 1 or g.stride != 1 or g.up0:
         return 1.0
     if wgrad:
         if g.C1 or g.C0 % 128 or W % 32:
