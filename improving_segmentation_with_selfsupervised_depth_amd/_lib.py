@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -89,6 +89,10 @@ _SIGS = {
     "segsde_bn_backward_workspace": (c_size_t, [c_long, c_int]),
     "segsde_bn_backward": (c_int, [P, c_int, P, c_int, P, c_int, c_long, c_int, P, P, P, P, c_int, c_float, c_uint64, c_int,
                                    P, P, P, c_int, P, c_int, P, c_size_t, P]),
+    "segsde_bn_mask_words": (c_size_t, [c_long, c_int]),
+    "segsde_bn_apply_mask": (c_int, [P, c_int, c_long, c_int, P, P, P, P, P, c_int, P, c_int, c_int, c_float, c_uint64, P, P]),
+    "segsde_bn_backward_mask": (c_int, [P, c_int, P, P, c_int, c_long, c_int, P, P, P, c_int, c_float, c_int, P, P, P, c_int, P, c_int,
+                                        P, c_size_t, P]),
     "segsde_colsum_workspace": (c_size_t, [c_long, c_int]),
     "segsde_act_backward": (c_int, [P, c_int, P, c_int, c_long, c_int, c_int, P, c_int, P, P, c_size_t, P]),
     "segsde_colsum": (c_int, [P, c_int, c_long, c_int, P, P, c_size_t, P]),

@@ -173,11 +173,30 @@ __global__ __launch_bounds__(256) void bn_eval_stats_kernel(const float* rm, con
   invstd[c] = 1.0f / sqrtf(rv[c] + eps);
 }
 
-template <int VW>
+// OR over the 8 lanes of an aligned lane octet, returned to each of them: two quad permutes and a half-row mirror (DPP, no LDS
+// traffic); the host interpreter of tests/hipemu runs the same exchange as three wave shuffles
+__device__ __forceinline__ unsigned octet_or(unsigned v) {
+#ifdef __HIP__
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);   // row_half_mirror: lane i <- lane 7 - i, the other quad
+#else
+  v |= (unsigned)__shfl_xor((int)v, 1); v |= (unsigned)__shfl_xor((int)v, 2); v |= (unsigned)__shfl_xor((int)v, 4);
+#endif
+  return v;
+}
+
+// MASK (VW = 4 only): also writes one bit per element of the logical [M][C] index space, bit (m * C + c) & 31 of word
+// (m * C + c) >> 5, set exactly when the stored y > 0 -- all that the backward pass of a residual ReLU BatchNorm needs of y
+// (segsde_act_grad_from_out).  A thread owns the 4 bits of its channel quad, 8 consecutive lanes own one word: the word is formed
+// in registers (octet_or) and stored by the octet's first lane.  Every word is written whole (zeros past the end of the index
+// space), so the buffer needs no fill.  The trip count is wave-uniform in this mode: the lanes past the end idle inside the loop.
+template <int VW, bool MASK = false>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* x, int ldx, long M, int C, const float* mean,
                                                        const float* invstd, const float* gamma, const float* beta,
                                                        const float* res, int ldr, float* y, int ldy, int act,
-                                                       float drop_p, uint64_t seed, int cv_shift) {
+                                                       float drop_p, uint64_t seed, int cv_shift, uint32_t* mask) {
+  static_assert(!MASK || VW == 4, "the mask words are built from channel quads");
   const int CV = C / VW;
   const long total = M * CV;
   const float keep_scale = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
@@ -204,22 +223,35 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* x, int ldx, 
       o.v[j] = t;
     }
     stv<VW>(y + m * ldy + c, o);
+    return o;
   };
   long e = blockIdx.x * 256L + threadIdx.x;
   // (four trips per thread at a time, all loads in flight together, measured SLOWER: 44.3 -> 49.0 us per launch; the column
   // sums, which only load, gained from the same unrolling)
-  for (; e < total; e += stride) {
-    // channel counts are powers of two on the whole ResNet / decoder path: shift + mask instead of a 64-bit division
-    const long m = cv_shift >= 0 ? (e >> cv_shift) : e / CV;
-    const int c = (int)(e - m * CV) * VW;
-    const VecF<VW> xv = ldv<VW>(x + m * ldx + c);
-    if (!fixed_c) {   // per-channel parameters as one 16-byte load each
-      mu = ldv<VW>(mean + c); is = ldv<VW>(invstd + c);
-      if (gamma) { ga = ldv<VW>(gamma + c); be = ldv<VW>(beta + c); }
+  for (; MASK ? (e & ~63L) < total : e < total; e += stride) {
+    unsigned bits = 0;
+    if (!MASK || e < total) {
+      // channel counts are powers of two on the whole ResNet / decoder path: shift + mask instead of a 64-bit division
+      const long m = cv_shift >= 0 ? (e >> cv_shift) : e / CV;
+      const int c = (int)(e - m * CV) * VW;
+      const VecF<VW> xv = ldv<VW>(x + m * ldx + c);
+      if (!fixed_c) {   // per-channel parameters as one 16-byte load each
+        mu = ldv<VW>(mean + c); is = ldv<VW>(invstd + c);
+        if (gamma) { ga = ldv<VW>(gamma + c); be = ldv<VW>(beta + c); }
+      }
+      VecF<VW> rv;
+      if (res) rv = ldv<VW>(res + m * ldr + c);
+      const VecF<VW> o = finish(m, c, xv, rv);
+      if constexpr (MASK) {
+#pragma unroll
+        for (int j = 0; j < VW; ++j) bits |= (o.v[j] > 0.f ? 1u : 0u) << j;
+      }
     }
-    VecF<VW> rv;
-    if (res) rv = ldv<VW>(res + m * ldr + c);
-    finish(m, c, xv, rv);
+    if constexpr (MASK) {
+      // e = m * CV + c / 4 is the quad's index in [M][C] order: lane l of an octet holds bits [4 l, 4 l + 4) of word e >> 3
+      const unsigned w = octet_or(bits << (4 * (threadIdx.x & 7)));
+      if ((threadIdx.x & 7) == 0 && e < total) mask[e >> 3] = w;
+    }
   }
 }
 
@@ -249,7 +281,15 @@ __device__ __forceinline__ float bn_dz_remask(float dy, float xh, float gamma, f
   return t > 0.f ? dy : 0.f;
 }
 
-struct BnBwdOp {
+// MASK ("bitmask"): the ReLU derivative comes from the packed bits bn_apply_kernel<4, true> wrote (y points at the words; ReLU,
+// no dropout, channel quads only): dz = dy * (bit ? 1 : 0), the product bn_dz forms from the saved output, so NaN / Inf / -0 in
+// dy propagate alike.  A thread's 4 channels share one word: one 4-byte load, its neighbours hit the same cache line.
+__device__ __forceinline__ unsigned bn_mask_quad(const uint32_t* mask, long m, int C, int c) {
+  const long i = m * C + c;              // a multiple of 4: the quad never straddles a word
+  return (mask[i >> 5] >> (unsigned)(i & 31)) & 15u;
+}
+template <bool MASK>
+struct BnBwdOpT {
   const float* dy; int lddy; const float* y; int ldy; const float* x; int ldx; const float* mean; const float* invstd;
   int act, C; float drop_p; uint64_t seed; const float* gamma; const float* beta;
   // per-channel parameters, loaded ONCE per thread (a thread of colreduce_kernel keeps its channels for all its rows)
@@ -262,6 +302,16 @@ struct BnBwdOp {
   }
   template <int VW> __device__ void row(long m, int c, const Ctx<VW>& k, double* s0, double* s1) const {
     const VecF<VW> g = ldv<VW>(dy + m * lddy + c), xx = ldv<VW>(x + m * ldx + c);
+    if constexpr (MASK) {
+      const unsigned bits = bn_mask_quad(reinterpret_cast<const uint32_t*>(y), m, C, c);
+#pragma unroll
+      for (int j = 0; j < VW; ++j) {
+        const float xh = (xx.v[j] - k.mu.v[j]) * k.is.v[j];
+        const float dz = g.v[j] * ((bits >> j) & 1u ? 1.f : 0.f);
+        s0[j] += (double)dz * (double)xh; s1[j] += (double)dz;
+      }
+      return;
+    }
     VecF<VW> yy;
     if (y) yy = ldv<VW>(y + m * ldy + c);
 #pragma unroll
@@ -273,6 +323,7 @@ struct BnBwdOp {
     }
   }
 };
+using BnBwdOp = BnBwdOpT<false>;
 
 __global__ __launch_bounds__(256) void pair_finalize_kernel(const double* part, int nb, int C, float* out0, float* out1) {
   SEGSDE_SMEM;
@@ -285,7 +336,7 @@ __global__ __launch_bounds__(256) void pair_finalize_kernel(const double* part, 
   if (out1) out1[c] = (float)b;
 }
 
-template <int VW>
+template <int VW, bool MASK = false>   // MASK: y points at the packed ReLU bits (see BnBwdOpT)
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int lddy, const float* y, int ldy,
                                                            const float* x, int ldx, long M, int C, const float* mean,
                                                            const float* invstd, const float* gamma, const float* beta,
@@ -295,7 +346,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int 
   const int CV = C / VW;
   const long total = M * CV;
   const float invM = 1.f / (float)M;
-  const bool remask = y == nullptr;
+  static_assert(!MASK || VW == 4, "the mask words are read per channel quad");
+  const bool remask = !MASK && y == nullptr;
   // per-channel parameters once per thread when every trip of the grid-stride loop meets the same channels (see bn_apply_kernel):
   // up to six 16-byte parameter loads next to the two or three data loads of a trip before
   const long stride = (long)gridDim.x * 256;
@@ -311,11 +363,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int 
     }
   };
   if (fixed_c) load_params((int)((blockIdx.x * 256L + threadIdx.x) & (long)(CV - 1)) * VW);
-  auto finish = [&](long m, int c, const VecF<VW>& g, const VecF<VW>& xx, const VecF<VW>& yy) {
+  auto finish = [&](long m, int c, const VecF<VW>& g, const VecF<VW>& xx, const VecF<VW>& yy, unsigned bits) {
     VecF<VW> dz, o;
 #pragma unroll
     for (int j = 0; j < VW; ++j) {
-      if (remask) dz.v[j] = bn_dz_remask(g.v[j], (xx.v[j] - mu.v[j]) * is.v[j], gamma ? ga.v[j] : 1.f, gamma ? be.v[j] : 0.f, gamma != nullptr, act);
+      if (MASK) dz.v[j] = g.v[j] * ((bits >> j) & 1u ? 1.f : 0.f);
+      else if (remask) dz.v[j] = bn_dz_remask(g.v[j], (xx.v[j] - mu.v[j]) * is.v[j], gamma ? ga.v[j] : 1.f, gamma ? be.v[j] : 0.f, gamma != nullptr, act);
       else dz.v[j] = bn_dz(g.v[j], yy.v[j], act, drop_p, seed, (uint64_t)(m * C + c + j));
       if (dx) {
         const float gm = gamma ? ga.v[j] : 1.f;
@@ -336,10 +389,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int 
     const int c = (int)(e - m * CV) * VW;
     const VecF<VW> g = ldv<VW>(dy + m * lddy + c);
     VecF<VW> xx, yy;
-    if (!remask) yy = ldv<VW>(y + m * ldy + c);
+    unsigned bits = 0;
+    if constexpr (MASK) bits = bn_mask_quad(reinterpret_cast<const uint32_t*>(y), m, C, c);
+    else if (!remask) yy = ldv<VW>(y + m * ldy + c);
     if ((dx && batch_stats) || remask) xx = ldv<VW>(x + m * ldx + c);
     if (!fixed_c) load_params(c);
-    finish(m, c, g, xx, yy);
+    finish(m, c, g, xx, yy, bits);
   }
 }
 
@@ -922,22 +977,43 @@ extern "C" int segsde_bn_eval_stats(const float* rm, const float* rv, int C, flo
   return 0;
 }
 
-extern "C" int segsde_bn_apply(const float* x, int ldx, long M, int C, const float* mean, const float* invstd,
-                               const float* gamma, const float* beta, const float* residual, int ldr, float* y, int ldy,
-                               int act, float drop_p, uint64_t seed, void* stream) {
+namespace {
+int bn_apply_impl(const float* x, int ldx, long M, int C, const float* mean, const float* invstd, const float* gamma,
+                  const float* beta, const float* residual, int ldr, float* y, int ldy, int act, float drop_p, uint64_t seed,
+                  uint32_t* mask, void* stream) {
   if (!x || !mean || !invstd || !y) return SEGSDE_ERR_NULL;
   if ((gamma == nullptr) != (beta == nullptr)) return SEGSDE_ERR_NULL;
   if (M <= 0 || C <= 0 || drop_p < 0.f || drop_p >= 1.f) return SEGSDE_ERR_SHAPE;
   const bool v4 = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && al16(x) && al16(y) &&
                   (!residual || ((ldr % 4 == 0) && al16(residual)));
-  if (v4)
+  if (mask) {   // the words are built per channel quad, and the dropout layers keep reading y
+    if (!v4 || drop_p > 0.f || (reinterpret_cast<uintptr_t>(mask) & 3)) return SEGSDE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((bn_apply_kernel<4, true>), dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), x, ldx, M, C,
+                       mean, invstd, gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, pow2_shift(C / 4), mask);
+  } else if (v4)
     hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), x, ldx, M, C, mean,
-                       invstd, gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, pow2_shift(C / 4));
+                       invstd, gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, pow2_shift(C / 4), (uint32_t*)nullptr);
   else
     hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_blocks_cv(M * C, C)), dim3(256), 0, ST(stream), x, ldx, M, C, mean, invstd,
-                       gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, pow2_shift(C));
+                       gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, pow2_shift(C), (uint32_t*)nullptr);
   SEGSDE_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int segsde_bn_apply(const float* x, int ldx, long M, int C, const float* mean, const float* invstd,
+                               const float* gamma, const float* beta, const float* residual, int ldr, float* y, int ldy,
+                               int act, float drop_p, uint64_t seed, void* stream) {
+  return bn_apply_impl(x, ldx, M, C, mean, invstd, gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, nullptr, stream);
+}
+
+extern "C" size_t segsde_bn_mask_words(long M, int C) { return M > 0 && C > 0 ? (size_t)((M * C + 31) / 32) : 0; }
+
+extern "C" int segsde_bn_apply_mask(const float* x, int ldx, long M, int C, const float* mean, const float* invstd,
+                                    const float* gamma, const float* beta, const float* residual, int ldr, float* y, int ldy,
+                                    int act, float drop_p, uint64_t seed, uint32_t* mask, void* stream) {
+  if (!mask) return SEGSDE_ERR_NULL;
+  return bn_apply_impl(x, ldx, M, C, mean, invstd, gamma, beta, residual, ldr, y, ldy, act, drop_p, seed, mask, stream);
 }
 
 extern "C" int segsde_bn_backward(const float* dy, int lddy, const float* y, int ldy, const float* x, int ldx, long M,
@@ -970,6 +1046,38 @@ extern "C" int segsde_bn_backward(const float* dy, int lddy, const float* y, int
       hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_blocks_cv(M * C, C)), dim3(256), 0, ST(stream), dy, lddy, y, ldy, x, ldx,
                          M, C, mean, invstd, gamma, beta, act, drop_p, seed, batch_stats, (const float*)dgamma,
                          (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C));
+    SEGSDE_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// third mode of the BatchNorm backward, next to "saved y" and "remask": the ReLU derivative is read from the bits
+// segsde_bn_apply_mask packed.  Same two reductions, same finalize, same apply arithmetic as segsde_bn_backward with the saved
+// output: dx, dres, dgamma and dbeta come out bit-identical.
+extern "C" int segsde_bn_backward_mask(const float* dy, int lddy, const uint32_t* mask, const float* x, int ldx, long M, int C,
+                                       const float* mean, const float* invstd, const float* gamma, int act, float drop_p,
+                                       int batch_stats, float* dgamma, float* dbeta, float* dx, int lddx, float* dres,
+                                       int lddres, void* ws, size_t ws_bytes, void* stream) {
+  if (!dy || !mask || !x || !mean || !invstd || !dgamma || !dbeta || !ws) return SEGSDE_ERR_NULL;
+  if (M <= 0 || C <= 0) return SEGSDE_ERR_SHAPE;
+  if (act != SEGSDE_ACT_RELU || drop_p != 0.f) return SEGSDE_ERR_UNSUPPORTED;
+  // channel quads only: there is no scalar flavour of this mode, the caller keeps the saved output for such shapes
+  const bool v4 = (C % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) && al16p(x) && al16p(dy) && (!gamma || al16p(gamma)) &&
+                  al16p(mean) && al16p(invstd) && (reinterpret_cast<uintptr_t>(mask) & 3) == 0 &&
+                  (!dx || ((lddx % 4 == 0) && al16p(dx))) && (!dres || ((lddres % 4 == 0) && al16p(dres))) &&
+                  al16p(dgamma) && al16p(dbeta);
+  if (!v4) return SEGSDE_ERR_UNSUPPORTED;
+  if (ws_bytes < part_bytes(M, C)) return SEGSDE_ERR_WORKSPACE;
+  const float* bits = reinterpret_cast<const float*>(mask);
+  BnBwdOpT<true> op{dy, lddy, bits, 0, x, ldx, mean, invstd, act, C, 0.f, 0, gamma, nullptr};
+  if (int e = launch_colreduce(op, M, C, (double*)ws, true, ST(stream))) return e;
+  hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws,
+                     red_blocks(M), C, dgamma, dbeta);
+  SEGSDE_CHECK_LAUNCH();
+  if (dx || dres) {
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), dy, lddy,
+                       bits, 0, x, ldx, M, C, mean, invstd, gamma, (const float*)nullptr, act, 0.f, (uint64_t)0, batch_stats,
+                       (const float*)dgamma, (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C / 4));
     SEGSDE_CHECK_LAUNCH();
   }
   return 0;

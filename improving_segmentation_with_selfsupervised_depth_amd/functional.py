@@ -30,6 +30,9 @@ class Function(_TorchFunction):
 # ``missed`` per kind (bench.py prints the per-step numbers, tests pin them for the models of the path) -- a maintainer who
 # inserts an op between a convolution and its BatchNorm sees ``bn_stats.missed`` go up instead of silently losing 8 % of a step.
 FUSIONS = {}
+# residual ReLU BatchNorms hand their backward pass a packed 1-bit mask instead of the saved output (BNActFn); False keeps the
+# saved-output route everywhere (A/B measurements, tests)
+BN_BITMASK = True
 
 
 def _grad_dest(param):
@@ -357,26 +360,38 @@ class BNActFn(Function):
                                       num_batches_tracked=nbt)
         else:
             mean, invstd = H.bn_eval_stats(running_mean, running_var, eps)
-        y = H.bn_apply(x, mean, invstd, gamma, beta, residual, act, drop_p, seed)
         # the backward pass reads the saved output only where the activation mask is not a function of x alone
         remask = act in ("none", "relu") and residual is None and not drop_p
+        # ... and of a ReLU after a residual add it needs one bit per element: the forward kernel packs them and both backward
+        # passes read those words instead of y (4 B -> 1/8 B per element and pass on bn3 / the downsample BN of every bottleneck)
+        mask = None
+        ctx.mask_route = bool(BN_BITMASK and act == "relu" and residual is not None and not drop_p)
+        if ctx.mask_route:
+            y, mask = H.bn_apply_mask(x, mean, invstd, gamma, beta, residual, act)
+        else:
+            y = H.bn_apply(x, mean, invstd, gamma, beta, residual, act, drop_p, seed)
         ctx.cfg = (act, drop_p, seed, training, residual is not None, remask)
         ctx.beta_param = beta          # (the parameter object: its gradient-bucket destination is looked up in backward)
-        ctx.save_for_backward(x, gamma, beta if remask else None, mean, invstd, None if remask else y)
+        # (y stays saved beside the bits: the next block keeps it alive anyway, and a gradient whose pitch the mask kernels do
+        # not take falls back to it)
+        ctx.save_for_backward(x, gamma, beta if remask else None, mean, invstd, None if remask else y, mask)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, beta, mean, invstd, y = ctx.saved_tensors
+        x, gamma, beta, mean, invstd, y, mask = ctx.saved_tensors
         act, drop_p, seed, training, has_res, remask = ctx.cfg
         want_g = gamma is not None and ctx.needs_input_grad[1]
         bp = ctx.beta_param
         dx, dres, dgamma, dbeta = H.bn_backward(_c(dy), y, x, mean, invstd, gamma, act, drop_p, seed, batch_stats=training,
                                                 need_dx=ctx.needs_input_grad[0],
-                                                need_dres=has_res and ctx.needs_input_grad[3], beta=beta,
+                                                need_dres=has_res and ctx.needs_input_grad[3], beta=beta, mask=mask,
                                                 dgamma_out=_grad_dest(gamma) if want_g else None,
                                                 dbeta_out=_grad_dest(bp) if (want_g and bp is not None and ctx.needs_input_grad[2]) else None)
         ctx.beta_param = None
+        if ctx.mask_route:
+            # counted from what the kernel did: shapes without a mask flavour ran this backward from the saved output
+            fusion("bn_backward_bitmask", mask is not None and bool(H.BN_MASK_USED[0]))
         if gamma is None or not ctx.needs_input_grad[1]:
             dgamma = dbeta = None
         if ctx.grad_box is not None and dres is not None:

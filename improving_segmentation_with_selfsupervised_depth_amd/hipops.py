@@ -1032,10 +1032,38 @@ def bn_apply(x, mean, invstd, gamma, beta, residual=None, act="none", drop_p=0.0
     return y
 
 
+def bn_apply_mask(x, mean, invstd, gamma, beta, residual=None, act="none"):
+    """bn_apply that also packs the sign of its output, one bit per element of the [M][C] index space (segsde_bn_apply_mask), for
+    bn_backward(mask=...).  Returns (y, mask); mask is None where the kernel has no mask flavour (channel counts that are no
+    multiple of 4, unaligned pitches / pointers) -- y then comes from the plain kernel and the backward pass reads it."""
+    M, C, ld = _rows(x)
+    L = _lib.lib()
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    ldr = _rows(residual)[2] if residual is not None else 0
+    nbytes = (8.0 + (4.0 if residual is not None else 0.0)) * M * C
+    if C % 4 == 0:
+        mask = torch.empty(L.segsde_bn_mask_words(M, C), dtype=torch.int32, device=x.device)
+        code = _timed('hbm_bn_apply', nbytes + 0.125 * M * C, x, lambda: L.segsde_bn_apply_mask(
+            _p(x), ld, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), ldr, _p(y), _rows(y)[2], ACT[act], 0.0, 0,
+            _p(mask), _stream(x)))
+        if code == 0:
+            return y, mask
+        if code != -4:
+            check(code, "bn_apply_mask")
+    _timed('hbm_bn_apply', nbytes, x, lambda: check(L.segsde_bn_apply(_p(x), ld, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), ldr, _p(y),
+                                                                       _rows(y)[2], ACT[act], 0.0, 0, _stream(x)), "bn_apply"))
+    return y, None
+
+
+BN_MASK_USED = _Slot(False)       # did the last bn_backward(mask=...) read the packed bits (functional.py counts from this)
+
+
 def bn_backward(dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, batch_stats=True, need_dx=True,
-                need_dres=False, beta=None, dgamma_out=None, dbeta_out=None):
+                need_dres=False, beta=None, dgamma_out=None, dbeta_out=None, mask=None):
     """y=None selects the remask mode of segsde_bn_backward (act none / plain ReLU: mask recomputed from x, beta needed).
-    dgamma_out / dbeta_out: dense [C] tensors to write into (gradient-bucket slices, ddp.grad_destination)."""
+    dgamma_out / dbeta_out: dense [C] tensors to write into (gradient-bucket slices, ddp.grad_destination).
+    mask: the bits bn_apply_mask packed (ReLU, no dropout): segsde_bn_backward_mask reads them in place of y, with bit-identical
+    results; where that entry does not take the call (pitch / alignment of dy or of the destinations) the saved y is read."""
     M, C, ldx = _rows(x)
     L = _lib.lib()
 
@@ -1047,6 +1075,18 @@ def bn_backward(dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, b
     dres = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dres else None
     nb = L.segsde_bn_backward_workspace(M, C)
     ws = _ws(nb, x)
+    BN_MASK_USED[0] = False
+    if mask is not None:
+        # both passes read dy, x and 1 bit per element: reduce 8.125, apply 8.125 + the tensors it writes
+        code = _timed('hbm_bn_backward', (16.25 + (4.0 if need_dx else 0.0) + (4.0 if need_dres else 0.0)) * M * C, x,
+                      lambda: L.segsde_bn_backward_mask(_p(_f32(dy)), _rows(dy)[2], _p(mask), _p(x), ldx, M, C, _p(mean), _p(invstd),
+                                                        _p(gamma), ACT[act], float(drop_p), int(batch_stats), _p(dgamma), _p(dbeta),
+                                                        _p(dx), C, _p(dres), C, _p(ws), nb, _stream(x)))
+        if code == 0:
+            BN_MASK_USED[0] = True
+            return dx, dres, dgamma, dbeta
+        if code != -4 or y is None:
+            check(code, "bn_backward_mask")
     _timed('hbm_bn_backward', (8.0 + (4.0 if y is not None else 0.0) + (4.0 if need_dx else 0.0) + (4.0 if need_dres else 0.0)) * M * C + 8.0 * M * C, x, lambda: check(L.segsde_bn_backward(_p(_f32(dy)), _rows(dy)[2], _p(y), _rows(y)[2] if y is not None else ldx, _p(x), ldx, M, C,
                                _p(mean), _p(invstd), _p(gamma), _p(beta), ACT[act], float(drop_p), int(seed), int(batch_stats), _p(dgamma), _p(dbeta),
                                _p(dx), C, _p(dres), C, _p(ws), nb, _stream(x)), "bn_backward"))

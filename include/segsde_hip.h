@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 15
+#define SEGSDE_ABI_VERSION 16
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -209,6 +209,21 @@ int segsde_bn_backward(const float* dy, int lddy, const float* y, int ldy, const
                        const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
                        float drop_p, uint64_t seed, int batch_stats, float* dgamma, float* dbeta, float* dx, int lddx,
                        float* dres, int lddres, void* workspace, size_t workspace_bytes, void* stream);
+/* Packed ReLU mask for the BatchNorms whose mask is not a function of x alone (residual add before the ReLU: bn3 and the
+ * downsample BN of a bottleneck, models/resnet_encoder.py).  segsde_bn_apply_mask is segsde_bn_apply plus one bit per element of
+ * the logical [M][C] index space: bit (m*C + c) % 32 of word (m*C + c) / 32 is 1 exactly when the stored y > 0;
+ * segsde_bn_mask_words(M, C) words, each written whole (zeros past the end), no fill needed.  segsde_bn_backward_mask is
+ * segsde_bn_backward with those bits in place of the saved output -- 1/32 B instead of 4 B per element and pass -- and gives
+ * bit-identical dx / dres / dgamma / dbeta.  Both need C % 4 == 0, pitches % 4 == 0 and 16-byte aligned tensors (the float4
+ * path), no dropout, and the backward act = ReLU: anything else returns SEGSDE_ERR_UNSUPPORTED and the caller keeps y. */
+size_t segsde_bn_mask_words(long M, int C);
+int segsde_bn_apply_mask(const float* x, int ldx, long M, int C, const float* mean, const float* invstd, const float* gamma,
+                         const float* beta, const float* residual, int ldr, float* y, int ldy, int act, float drop_p,
+                         uint64_t seed, uint32_t* mask, void* stream);
+int segsde_bn_backward_mask(const float* dy, int lddy, const uint32_t* mask, const float* x, int ldx, long M, int C,
+                            const float* mean, const float* invstd, const float* gamma, int act, float drop_p,
+                            int batch_stats, float* dgamma, float* dbeta, float* dx, int lddx, float* dres, int lddres,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* dz = dy * act'(y) (ELU / ReLU / sigmoid via the saved output, as the reference's in-place ops do);
  * dbias[c] = sum_rows dz (nullable).  Replaces autograd of nn.ELU / nn.ReLU / torch.sigmoid + conv bias grad. */
 size_t segsde_colsum_workspace(long M, int C);
