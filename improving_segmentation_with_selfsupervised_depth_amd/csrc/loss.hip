@@ -60,7 +60,7 @@ __device__ __forceinline__ Geo geometry(const float* disp_b, int hs, int ws, int
   g.in_y = iy > 0.f && iy < (float)(H - 1);
   ix = fminf(fmaxf(ix, 0.f), (float)(W - 1));
   iy = fminf(fmaxf(iy, 0.f), (float)(H - 1));
-  if (!(ix == ix)) ix = 0.f;   // NaN guard (ATen clamps NaN through fmin/fmax the same way: result max())
+  if (!(ix == ix)) ix = 0.f;   // NaN guard: ATen's border clamp takes a NaN coordinate to 0 as well (it samples pixel (0, 0))
   if (!(iy == iy)) iy = 0.f;
   g.ix = ix; g.iy = iy;
   return g;
