@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -26,6 +26,12 @@ class PackJob(ctypes.Structure):
 class WinoJob(ctypes.Structure):
     """mirror of ``segsde_wino_job`` (include/segsde_hip.h)"""
     _fields_ = [("w", c_void_p), ("u_fwd", c_void_p), ("u_dgrad", c_void_p)] + [(n, c_int) for n in ("O", "I", "block0", "reserved")]
+
+
+class BnFoldJob(ctypes.Structure):
+    """mirror of ``segsde_bn_fold_job`` (include/segsde_hip.h)"""
+    _fields_ = [(n, c_void_p) for n in ("w", "cb", "gamma", "beta", "mean", "var", "w_out", "b_out")] + [("eps", c_float)] + [
+        (n, c_int) for n in ("O", "I", "KH", "KW", "block0", "reserved")]
 
 
 class ConvDesc(ctypes.Structure):
@@ -46,6 +52,7 @@ _SIGS = {
     "segsde_conv2d_dgrad_actgrad": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, c_int, c_int, P]),
     "segsde_bn_stats_from_partials_workspace": (c_size_t, [c_int]),
     "segsde_bn_stats_from_partials": (c_int, [P, c_long, c_long, c_int, P, P, P, P, c_float, c_float, P, P, c_size_t, P]),
+    "segsde_conv2d_forward_residual": (c_int, [POINTER(ConvDesc), P, P, P, P, P, c_int, P, P]),
     "segsde_conv2d_wgrad_workspace": (c_size_t, [POINTER(ConvDesc)]),
     "segsde_conv2d_wgrad": (c_int, [POINTER(ConvDesc), P, P, P, c_int, P, P, c_size_t, P]),
     "segsde_conv2d_winograd_workspace": (c_size_t, [POINTER(ConvDesc)]),
@@ -75,6 +82,7 @@ _SIGS = {
     "segsde_stem_pack": (c_int, [P, c_int, c_int, c_int, P, P]),
     "segsde_stem7x7_stats_rows": (c_long, [c_int, c_int, c_int, c_int, c_int]),
     "segsde_stem7x7_forward": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P]),
+    "segsde_stem7x7_forward_bias_act": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P, P]),
     "segsde_stem7x7_wgrad_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "segsde_stem7x7_wgrad": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_size_t, P]),
     "segsde_nchw_to_nhwc_bordered": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, P]),
@@ -85,6 +93,7 @@ _SIGS = {
     "segsde_bn_stats_workspace": (c_size_t, [c_long, c_int]),
     "segsde_bn_stats": (c_int, [P, c_int, c_long, c_int, P, P, P, P, c_float, c_float, P, P, c_size_t, P]),
     "segsde_bn_eval_stats": (c_int, [P, P, c_int, c_float, P, P, P]),
+    "segsde_bn_fold": (c_int, [P, c_int, c_int, P]),
     "segsde_bn_apply": (c_int, [P, c_int, c_long, c_int, P, P, P, P, P, c_int, P, c_int, c_int, c_float, c_uint64, P]),
     "segsde_bn_backward_workspace": (c_size_t, [c_long, c_int]),
     "segsde_bn_backward": (c_int, [P, c_int, P, c_int, P, c_int, c_long, c_int, P, P, P, P, c_int, c_float, c_uint64, c_int,

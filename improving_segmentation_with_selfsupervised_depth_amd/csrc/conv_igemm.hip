@@ -77,6 +77,10 @@ struct ConvP {
   // whose first row lies in image b of the B-image input reads its weight rows from w + b * wbstride floats.  0: one weight.
   long wbstride;
   int cmp;      // operand arithmetic asked of the LDS-DMA loops (segsde_conv_desc.compute): 1 fp16, 2 split bf16 (nine products)
+  // Residual operand of the staged epilogue (segsde_conv2d_forward_residual, nullable): y = act((acc + bias) + res), res in the row /
+  // channel order of y with pixel pitch ldr.  Single destination, plain row mapping (no sub-grids); res may BE y (same pitch):
+  // a thread loads the residual values of exactly the elements it stores, before it stores them.
+  const float* res; int ldr;
 };
 constexpr int SEGSDE_PAD_CLAMP_ = 3;   // internal (never crosses the ABI)
 
@@ -877,7 +881,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvP p) {
       };
       // an accumulating launch (the skip-source half of an upsample-folded convolution) activates AFTER adding what the
       // destination holds: only the bias goes in here
-      if (pe.accum) put([](float v) { return v; });
+      // (and so does a launch with a residual operand: the activation follows the residual add)
+      if (pe.accum || pe.res) put([](float v) { return v; });
       else if (pe.act == SEGSDE_ACT_ELU) put([](float v) { return v > 0.f ? v : __expf(fminf(v, 0.f)) - 1.f; });
       else if (pe.act == SEGSDE_ACT_RELU) put([](float v) { return fmaxf(v, 0.f); });
       else if (pe.act == SEGSDE_ACT_SIGMOID) put([](float v) { return segsde_act(v, SEGSDE_ACT_SIGMOID); });
@@ -936,6 +941,33 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvP p) {
         const unsigned stepa = (unsigned)RPP * agl * 4u;
         const float* cp = Ct + rr * BN + 4 * cq;
         float4 o[NR];
+        if (pe.res) {
+          // frozen BatchNorm folded into the weights, residual block: act((acc + bias) + res).  A loop of its own for the reason
+          // given at the accumulating one below; every residual load is issued before the first store (res may be y itself)
+          const unsigned lr = (unsigned)pe.ldr;
+          const segsde_rsrc rs = segsde_make_rsrc(pe.res + (row0 * pe.ldr + n0));
+          const unsigned vr = n < pe.ne ? ((unsigned)rr * lr + 4u * cq) * 4u : SEGSDE_OOB;
+          const unsigned stepr = (unsigned)RPP * lr * 4u;
+          unsigned sr = 0, so = 0;
+#pragma unroll
+          for (int t = 0; t < NR; ++t) { o[t] = segsde_buffer_load4(rs, vr, sr); sr += stepr; }
+#pragma unroll
+          for (int t = 0; t < NR; ++t) {
+            float4 v = *reinterpret_cast<const float4*>(cp + t * RPP * BN);
+            v.x += o[t].x; v.y += o[t].y; v.z += o[t].z; v.w += o[t].w;
+            if (pe.act == SEGSDE_ACT_RELU) {
+              v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            } else if (pe.act == SEGSDE_ACT_ELU) {
+              v.x = v.x > 0.f ? v.x : __expf(fminf(v.x, 0.f)) - 1.f; v.y = v.y > 0.f ? v.y : __expf(fminf(v.y, 0.f)) - 1.f;
+              v.z = v.z > 0.f ? v.z : __expf(fminf(v.z, 0.f)) - 1.f; v.w = v.w > 0.f ? v.w : __expf(fminf(v.w, 0.f)) - 1.f;
+            } else if (pe.act != SEGSDE_ACT_NONE) {
+              v.x = segsde_act(v.x, pe.act); v.y = segsde_act(v.y, pe.act); v.z = segsde_act(v.z, pe.act); v.w = segsde_act(v.w, pe.act);
+            }
+            segsde_buffer_store4(rd, vo, so, v);
+            so += step;
+          }
+          return;
+        }
         if (pe.accum) {
           unsigned so = 0;
 #pragma unroll
@@ -980,7 +1012,35 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvP p) {
       float* dst; long ld; int nn;
       if (n < pe.nsplit) { dst = pe.y; ld = pe.ldy; nn = n; }
       else { dst = pe.y2; ld = pe.ldy2; nn = n - pe.nsplit; }
-      if (pe.accum) {
+      if (pe.res) {
+        // the residual launch on a ragged tile (rows past M, a sub-grid never: single destination, plain rows): all residual
+        // loads of a thread first, as in the accumulating branch below -- and because res may be y
+        constexpr int NR = BM / RPP;
+        float4 o[NR];
+#pragma unroll
+        for (int t = 0; t < NR; ++t) {
+          const int m = m0 + rr + t * RPP;
+          o[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (m < pe.M) o[t] = *reinterpret_cast<const float4*>(pe.res + (long)m * pe.ldr + nn);
+        }
+#pragma unroll
+        for (int t = 0; t < NR; ++t) {
+          const int ml = rr + t * RPP, m = m0 + ml;
+          if (m < pe.M) {
+            float4 v = *reinterpret_cast<const float4*>(Ct + ml * BN + 4 * cq);
+            v.x += o[t].x; v.y += o[t].y; v.z += o[t].z; v.w += o[t].w;
+            if (pe.act == SEGSDE_ACT_RELU) {
+              v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            } else if (pe.act == SEGSDE_ACT_ELU) {
+              v.x = v.x > 0.f ? v.x : __expf(fminf(v.x, 0.f)) - 1.f; v.y = v.y > 0.f ? v.y : __expf(fminf(v.y, 0.f)) - 1.f;
+              v.z = v.z > 0.f ? v.z : __expf(fminf(v.z, 0.f)) - 1.f; v.w = v.w > 0.f ? v.w : __expf(fminf(v.w, 0.f)) - 1.f;
+            } else if (pe.act != SEGSDE_ACT_NONE) {
+              v.x = segsde_act(v.x, pe.act); v.y = segsde_act(v.y, pe.act); v.z = segsde_act(v.z, pe.act); v.w = segsde_act(v.w, pe.act);
+            }
+            *reinterpret_cast<float4*>(dst + (long)m * ld + nn) = v;
+          }
+        }
+      } else if (pe.accum) {
         // y += tile: every read-modify-write of a row segment depends on a global load; issue all of a thread's loads
         // first (the accumulators are in LDS by now, registers are free) so that their latency is paid once, not
         // BM / RPP times in a row -- on the 8-chunk 1x1 data-gradients this epilogue was a third of the tile's time
@@ -1801,6 +1861,7 @@ ConvP make_params(const segsde_conv_desc* d, const float* x0, const float* x1, c
   p.tapskip = (d->pad_mode == SEGSDE_PAD_ZERO && d->dil > 1 && d->KH > 1 && d->in_div <= 1 && !d->up0 && !d->sum2x2 &&
                d->stride == 1) ? 1 : 0;
   p.wbstride = 0;
+  p.res = nullptr; p.ldr = 0;
   return p;
 }
 
@@ -2175,6 +2236,29 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
     // the generic gathers treat the padding as zeros; add the mirrored-padding contributions on the border pixels
     return launch_reflect_fix(x0, p.ld0, wpack, y, p.ldy, y2, p.ldy2, p.nsplit, p.B, p.H, p.W, p.N, p.C0, s);
   return 0;
+}
+
+extern "C" int segsde_conv2d_forward_residual(const segsde_conv_desc* d, const float* x0, const float* x1, const float* wpack,
+                                              const float* bias, const float* res, int ldr, float* y, void* stream) {
+  if (int e = validate(d)) return e;
+  if (!x0 || !wpack || !res || !y || (d->C1 && !x1)) return SEGSDE_ERR_NULL;
+  if (ldr < d->Cout || d->ldy < d->Cout) return SEGSDE_ERR_SHAPE;
+  // res may be y itself (same pitch: every thread reads what it is about to overwrite, nothing else); any other overlap of the
+  // two extents would let one workgroup read what another has already written
+  if (!(res == y && ldr == d->ldy)) {
+    const long M = (long)d->B * d->Ho * d->Wo;
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(res), r1 = r0 + ((M - 1) * ldr + d->Cout) * sizeof(float);
+    const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + ((M - 1) * d->ldy + d->Cout) * sizeof(float);
+    if (r0 < y1 && y0 < r1) return SEGSDE_ERR_SHAPE;
+  }
+  // one destination through the staged (vector) epilogue, plain rows: everything else runs unfused at the caller
+  if (d->act < SEGSDE_ACT_NONE || d->act > SEGSDE_ACT_SIGMOID || d->sum2x2 || d->in_div > 1 || d->accumulate || d->Cout == 1 ||
+      d->pad_mode == SEGSDE_PAD_REFLECT_ADJOINT || d->nsplit || d->ldy2 || (ldr % 4) || !aligned16(res))
+    return SEGSDE_ERR_UNSUPPORTED;
+  ConvP p = make_params(d, x0, x1, wpack, bias, y, nullptr);
+  if (!p.vecout) return SEGSDE_ERR_UNSUPPORTED;
+  p.res = res; p.ldr = ldr;
+  return launch_by_n(p, static_cast<hipStream_t>(stream));
 }
 
 namespace {
@@ -2788,6 +2872,17 @@ extern "C" int segsde_stem7x7_forward(const float* xpad, int B, int Hp, int Wp, 
     if (stats_rows(&c, p) == 0) return SEGSDE_ERR_UNSUPPORTED;
     p.stats = stats;
   }
+  return launch_by_n(p, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int segsde_stem7x7_forward_bias_act(const float* xpad, int B, int Hp, int Wp, int cp, const float* wstem, int Cout,
+                                               const float* bias, int act, float* y, void* stream) {
+  if (!xpad || !wstem || !y) return SEGSDE_ERR_NULL;
+  segsde_conv_desc c;
+  if (!stem_desc(B, Hp, Wp, cp, Cout, c) || act < SEGSDE_ACT_NONE || act > SEGSDE_ACT_SIGMOID) return SEGSDE_ERR_SHAPE;
+  c.act = act;
+  ConvP p = make_params(&c, xpad, nullptr, wstem, bias, y, nullptr);
+  if (!igemm_fast_ok(p) || !p.vecout) return SEGSDE_ERR_UNSUPPORTED;
   return launch_by_n(p, static_cast<hipStream_t>(stream));
 }
 

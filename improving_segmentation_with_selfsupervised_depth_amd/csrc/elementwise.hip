@@ -978,6 +978,44 @@ extern "C" int segsde_bn_eval_stats(const float* rm, const float* rv, int C, flo
 }
 
 namespace {
+// every (convolution, frozen BatchNorm) pair of a model in ONE launch (the job table of pack_weight_multi_kernel): job j owns
+// blocks [block0, next job's block0), one element per thread and trip.  s is recomputed per element from three cached loads
+// (the launch runs once per weight version, not per step); invstd is bn_eval_stats_kernel's expression, so both paths share
+// its bits.  Plain fp32 in the order written (the sources are compiled with -ffp-contract=off).
+__global__ __launch_bounds__(256) void bn_fold_kernel(const segsde_bn_fold_job* jobs, int njobs) {
+  int lo = 0, hi = njobs;                       // jobs[j].block0 <= blockIdx.x < jobs[j + 1].block0 (sentinel at njobs)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int)blockIdx.x >= jobs[mid].block0) lo = mid; else hi = mid;
+  }
+  const segsde_bn_fold_job j = jobs[lo];
+  const long nblk = jobs[lo + 1].block0 - j.block0, lb = (long)blockIdx.x - j.block0;
+  const long per = (long)j.I * j.KH * j.KW, total = (long)j.O * per;
+  for (long e = lb * 256 + threadIdx.x; e < total; e += nblk * 256) {
+    const int o = (int)(e / per);
+    const float invstd = 1.0f / sqrtf(j.var[o] + j.eps);
+    const float s = j.gamma ? j.gamma[o] * invstd : invstd;
+    j.w_out[e] = j.w[e] * s;
+  }
+  for (long o = lb * 256 + threadIdx.x; o < j.O; o += nblk * 256) {
+    const float invstd = 1.0f / sqrtf(j.var[o] + j.eps);
+    const float s = j.gamma ? j.gamma[o] * invstd : invstd;
+    float t = (j.beta ? j.beta[o] : 0.f) - j.mean[o] * s;
+    if (j.cb) t = t + j.cb[o] * s;
+    j.b_out[o] = t;
+  }
+}
+}  // namespace
+
+extern "C" int segsde_bn_fold(const segsde_bn_fold_job* jobs_device, int njobs, int total_blocks, void* stream) {
+  if (!jobs_device) return SEGSDE_ERR_NULL;
+  if (njobs <= 0 || total_blocks <= 0) return SEGSDE_ERR_SHAPE;
+  hipLaunchKernelGGL(bn_fold_kernel, dim3(total_blocks), dim3(256), 0, ST(stream), jobs_device, njobs);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
 int bn_apply_impl(const float* x, int ldx, long M, int C, const float* mean, const float* invstd, const float* gamma,
                   const float* beta, const float* residual, int ldr, float* y, int ldy, int act, float drop_p, uint64_t seed,
                   uint32_t* mask, void* stream) {

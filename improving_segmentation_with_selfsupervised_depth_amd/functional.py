@@ -91,6 +91,33 @@ class conv_compute:
         return False
 
 
+# Frozen BatchNorm folded into the convolution in front of it, in no-grad forward passes (models/layers.conv_bn): off unless
+# SEGSDE_FROZEN_BN_FOLD=1 (read once, here) or inside ``with frozen_bn_fold():``
+FROZEN_BN_FOLD = [__import__("os").environ.get("SEGSDE_FROZEN_BN_FOLD", "0") not in ("0", "")]
+
+
+class frozen_bn_fold:
+    """``with frozen_bn_fold():`` -- inside, a convolution followed by a BatchNorm in eval mode, called under ``torch.no_grad()``,
+    runs as ONE launch: the BatchNorm's per-channel affine is folded into the weights and a bias (hipops.bn_fold), residual add and
+    activation ride in the convolution's epilogue, and the normalisation pass over the tensor (one read, one write) is gone
+    (models/layers.conv_bn decides per pair; ``fusion_report()["frozen_bn_folded"]`` counts).  fp32 re-associated: within 3x of
+    the unfused path's error against float64 (profiles/frozen_bn_fold.md).  ``frozen_bn_fold(False)`` switches it off inside an
+    enclosing scope; the previous state is restored on exit.  Training-mode BatchNorms, passes with gradients enabled and
+    BatchNorms with dropout are untouched."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = FROZEN_BN_FOLD[0]
+        FROZEN_BN_FOLD[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        FROZEN_BN_FOLD[0] = self.old
+        return False
+
+
 def fusion(kind, taken):
     c = FUSIONS.setdefault(kind, [0, 0])
     c[0 if taken else 1] += 1

@@ -660,10 +660,13 @@ def pack_weights_multi(weights):
     return views
 
 
-def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=None, wino=None, keep_v=False):
+def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=None, wino=None, keep_v=False, residual=None):
     """y = act(conv(cat[up?(x0), x1]) + bias).  x0: [B,H0,W0,C0] (H0 = H/2 if g.up0), x1: [B,H,W,C1] or None.
     want_stats: also return the per-tile statistics partials of y for the BatchNorm that follows ([rows,2,Cout] doubles,
-    or None when this shape cannot fuse them) -> (y, partials)."""
+    or None when this shape cannot fuse them) -> (y, partials).
+    residual: [B,Ho,Wo,Cout] added before the activation, y = act((conv + bias) + residual), on the direct route only
+    (segsde_conv2d_forward_residual; no statistics, no Winograd / folded route) -> y, or None when the launch declines the shape
+    (the caller then runs the unfused sequence)."""
     B, H0, W0, C0 = x0.shape
     H, W = (2 * H0, 2 * W0) if g.up0 else (H0, W0)
     assert C0 == g.C0 and (g.C1 == 0) == (x1 is None)
@@ -677,6 +680,16 @@ def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=Non
                  act=ACT[act], sum2x2=0, compute=g.compute)
     flops = 2.0 * B * Ho * Wo * g.Cout * g.CinAlg * g.k * g.k
     flops_x = flops * g.Cin / g.CinAlg * _live_tap_frac(g, H, W)   # executed: zero pad channels of a stem are multiplied too, dead tap rows are not
+    if residual is not None:
+        assert not want_stats and wfold is None and wino is None and tuple(residual.shape) == tuple(y.shape)
+        rc = _timed("conv_fwd", flops, x0, lambda: _lib.lib().segsde_conv2d_forward_residual(
+            ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(bias), _p(_f32(residual)), nhwc_ld(residual), _p(y), _stream(x0)),
+            _tag(g, H, W) + " res", executed=flops_x)
+        if rc == -4:
+            return None
+        check(rc, "conv2d_forward_residual")
+        _note_compute(d, 0, "fwd")
+        return y
     if isinstance(wino, _KnPack):
         if (not want_stats or (bias is None and act == "none")) and winograd_fused_ok(g, B, H, W):
             r = winograd_fused("conv_fwd", x0, wino, bias=bias, act=act, want_stats=want_stats, tag=_tag(g, H, W), reflect=g.reflect,
@@ -1023,6 +1036,36 @@ def bn_eval_stats(running_mean, running_var, eps):
     return mean, invstd
 
 
+def bn_fold(pairs, cb=None, gamma=None, beta=None, running_mean=None, running_var=None, eps=1e-5):
+    """A frozen BatchNorm folded into the convolution in front of it (segsde_bn_fold): ``bn_fold(w, cb, gamma, beta, running_mean,
+    running_var, eps) -> (w', b')`` with w' = w * s per output channel, b' = beta - running_mean * s (+ cb * s), s = gamma /
+    sqrt(running_var + eps); cb / gamma / beta may be None (no conv bias; affine=False).  ``bn_fold([(w, cb, gamma, beta,
+    running_mean, running_var, eps), ...]) -> [(w', b'), ...]``: the pairs of a whole model in ONE launch."""
+    single = isinstance(pairs, torch.Tensor)
+    if single:
+        pairs = [(pairs, cb, gamma, beta, running_mean, running_var, eps)]
+    assert pairs
+    dev = pairs[0][0].device
+    jobs = (_lib.BnFoldJob * (len(pairs) + 1))()
+    outs, keep, blk = [], [], 0
+    for i, (w, b, ga, be, rm, rv, e) in enumerate(pairs):
+        w = _f32(w.detach(), "weight").contiguous()
+        O, I, KH, KW = w.shape
+        vecs = [None if t is None else _f32(t.detach()).contiguous() for t in (b, ga, be, rm, rv)]
+        assert vecs[3] is not None and vecs[4] is not None and all(t is None or (t.numel() == O and t.device == dev) for t in vecs)
+        assert w.device == dev
+        wo, bo = torch.empty_like(w), torch.empty(O, dtype=torch.float32, device=dev)
+        jobs[i] = _lib.BnFoldJob(w.data_ptr(), *[0 if t is None else t.data_ptr() for t in vecs], wo.data_ptr(), bo.data_ptr(),
+                                 float(e), O, I, KH, KW, blk, 0)
+        blk += max(1, min(2048, (w.numel() + 1023) // 1024))
+        outs.append((wo, bo))
+        keep.append((w, vecs))                       # contiguous copies stay alive until the launch is queued
+    jobs[len(pairs)] = _lib.BnFoldJob(0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0, 0, blk, 0)
+    raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+    check(_lib.lib().segsde_bn_fold(_p(raw), len(pairs), blk, _stream(outs[0][0])), "bn_fold")
+    return outs[0] if single else outs
+
+
 def bn_apply(x, mean, invstd, gamma, beta, residual=None, act="none", drop_p=0.0, seed=0, out=None):
     M, C, ld = _rows(x)
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device) if out is None else out
@@ -1310,8 +1353,9 @@ def stem_pack(weight):
     return out
 
 
-def stem_forward(xpad, wstem, C, want_stats=False):
-    """xpad: stem_input(); wstem: stem_pack(); C: real input planes (FLOP accounting) -> y [B, Ho, Wo, Cout] (, partials)"""
+def stem_forward(xpad, wstem, C, want_stats=False, bias=None, act="none"):
+    """xpad: stem_input(); wstem: stem_pack(); C: real input planes (FLOP accounting) -> y [B, Ho, Wo, Cout] (, partials).
+    bias / act: y = act(conv + bias) through segsde_stem7x7_forward_bias_act (the stem behind a folded frozen BatchNorm)"""
     B, Hp, Wp, cp = xpad.shape
     Cout = wstem.shape[0]
     H, W = Hp - 6, Wp - 8
@@ -1323,6 +1367,13 @@ def stem_forward(xpad, wstem, C, want_stats=False):
         if rows > 0:
             part = torch.empty((rows, 2, Cout), dtype=torch.float64, device=xpad.device)
     flops = 2.0 * B * Ho * Wo * Cout * C * 49
+    if bias is not None or act != "none":
+        assert not want_stats
+        _timed("conv_fwd", flops, xpad, lambda: check(_lib.lib().segsde_stem7x7_forward_bias_act(
+            _p(xpad), B, Hp, Wp, cp, _p(wstem), Cout, _p(bias), ACT[act], _p(y), _stream(xpad)), "stem7x7_forward_bias_act"),
+            "stem c%d k7 s2 %dx%d" % (C, H, W), executed=2.0 * B * Ho * Wo * Cout * 56 * cp)
+        STEM_TAKEN["fwd"] += 1
+        return y
     _timed("conv_fwd", flops, xpad, lambda: check(_lib.lib().segsde_stem7x7_forward(
         _p(xpad), B, Hp, Wp, cp, _p(wstem), Cout, _p(y), _p(part), _stream(xpad)), "stem7x7_forward"),
         "stem c%d k7 s2 %dx%d" % (C, H, W), executed=2.0 * B * Ho * Wo * Cout * 56 * cp)

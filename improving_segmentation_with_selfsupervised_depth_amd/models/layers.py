@@ -89,6 +89,7 @@ class Conv2d(nn.Conv2d):
         self._pack_key, self._packs = None, None   # weight packs of the current weight version (see _weight_packs)
         self._fold_cache = {}         # upsample-folded packs of the same weight version (filled by ConvFn inside a pack scope)
         self._wino_cache = {}         # Winograd-transformed packs, likewise
+        self._bn_fold = {}            # frozen-BatchNorm-folded weight, bias and their packs (see conv_bn); independent of pack scopes
         self._stats_wanted = None     # None: unknown yet, True: a BatchNorm consumed the fused statistics, False: nobody did
         self._stats_offered = False
         k = self.kernel_size[0]
@@ -214,3 +215,101 @@ class BatchNorm2d(nn.BatchNorm2d):
             Fn.fusion("bn_stats_from_conv_epilogue", partials is not None)
         return Fn.BNActFn.apply(x, self.weight, self.bias, residual, self.running_mean, self.running_var, training,
                                 momentum, self.eps, act, drop_p, seed, partials, grad_box, nbt)
+
+
+def _tensor_key(t):
+    return None if t is None else (t._version, t.data_ptr(), t.device)
+
+
+def _folded(conv, bn):
+    """The cache entry of ``conv`` folded with the frozen ``bn``: {"w": w * s (OIHW), "b": beta - mean * s (+ conv bias * s)} plus
+    the packs derived from them, filled in by the routes as they are first taken.  Keyed on version counter, storage and device
+    of the six tensors involved, eps and the BatchNorm's identity: an optimiser step, an EMA update that bumps the versions
+    (trainer.EMA), ``load_state_dict`` or any in-place edit re-folds at the next forward; a frozen network hits the cache every
+    time.  Not caught, as for weight_pack_scope: writes through ``param.data`` (they bump no version counter) -- after such a
+    write call ``drop_folded(model)``."""
+    key = (id(bn), float(bn.eps)) + tuple(_tensor_key(t) for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
+                                                                     bn.running_var))
+    e = conv.__dict__["_bn_fold"]
+    if e.get("key") != key:
+        w, b = H.bn_fold(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        e.clear()
+        e.update(key=key, w=w, b=b)
+    return e
+
+
+def drop_folded(model):
+    """forget the folded weights of every convolution of ``model`` (after parameters were rewritten behind the version counters)"""
+    for m in model.modules():
+        if isinstance(m, Conv2d):
+            m._bn_fold.clear()
+
+
+def _folded_forward(conv, bn, x, residual, act, image_norm):
+    """conv -> frozen bn (-> + residual) -> act as one launch on the folded weights, through the route the convolution would take
+    anyway (stem, one-kernel Winograd, grouped Winograd, direct); None when this pair stays unfused"""
+    if image_norm is not None:
+        mean, std = image_norm
+        if H.stem_ok(x, conv):
+            e = _folded(conv, bn)
+            if "stem" not in e:
+                e["stem"] = H.stem_pack(e["w"])
+            return H.stem_forward(H.stem_input(x, mean, std), e["stem"], conv.in_channels, bias=e["b"], act=act)
+        x = Fn.to_nhwc(x, mean, std, pad_to=4)
+    if x.stride(-1) != 1:
+        x = Fn._c(x)
+    B, Hh, W, c0 = x.shape
+    assert c0 >= conv.in_channels
+    g = ConvGeom(c0, conv.out_channels, conv.kernel_size[0], conv.stride[0], conv.dilation[0], conv.padding[0], conv.reflect, 0, False,
+                 cin_alg=conv.in_channels if c0 > conv.in_channels else None)
+    if residual is not None and conv.kernel_size == (3, 3) and conv.stride == (1, 1):
+        # BasicBlock.conv2: the Winograd geometry, and the Winograd routes take no residual operand -- this pair keeps its
+        # normalisation pass whatever route its size selects (one rule, so the count does not depend on the image size)
+        return None
+    kn = H.winograd_fused_ok(g, B, Hh, W)
+    wino = kn or H.winograd_ok(g, B, Hh, W)
+    e = _folded(conv, bn)
+    pk = ("pack", c0)
+    if pk not in e:
+        w = e["w"]
+        if c0 > conv.in_channels:          # zero pad channels of a stem input: matching zero weight planes (Conv2d.forward)
+            w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, c0 - conv.in_channels))
+        e[pk] = H.pack_weight(w, False)
+    if residual is not None:
+        if residual.stride(-1) != 1:
+            residual = Fn._c(residual)
+        return H.conv_forward(g, x, None, e[pk], e["b"], act, residual=residual)
+    wino_f = None
+    if wino:
+        wk = ("wino", bool(kn))
+        if wk not in e:
+            e[wk] = H.winograd_pack(e["w"], kn=bool(kn))[0]
+        wino_f = e[wk]
+    return H.conv_forward(g, x, None, e[pk], e["b"], act, wino=wino_f)
+
+
+def conv_bn(conv, bn, x, residual=None, act="none", drop_p=0.0, bn_grad_box=None, image_norm=None, **conv_kwargs):
+    """``bn(conv(x, **conv_kwargs), residual=residual, act=act)`` -- the one place that decides whether a convolution and the
+    BatchNorm behind it run as one launch (Fn.frozen_bn_fold).  The folded route is taken only when the switch is on, gradients are
+    disabled, ``bn`` is in eval mode with running statistics and no dropout is requested; otherwise, and for a pair the kernels
+    decline (a residual behind a Winograd convolution, a shape without the vector epilogue), exactly the unfused expression runs
+    on the original weights.  Every decision made with the switch on is counted: Fn.fusion("frozen_bn_folded", taken).
+    image_norm = (mean, std): ``x`` is the NCHW image of a network stem and the convolution is Conv2d.forward_image's
+    ((x - mean) / std, then the 7x7 / stride-2 stem kernel, or to_nhwc + forward for any other geometry).
+    The folded weight, bias and their packs are cached on ``conv`` (see _folded): this doubles the weight memory of the folded
+    modules -- about 170 MB for a ResNet-101 encoder -- for as long as the module lives or until drop_folded()."""
+    if Fn.FROZEN_BN_FOLD[0]:
+        ok = (not torch.is_grad_enabled() and not bn.training and bn.running_mean is not None and bn.running_var is not None
+              and not drop_p > 0 and not conv_kwargs.get("up") and conv_kwargs.get("skip") is None
+              and conv_kwargs.get("act", "none") == "none")
+        y = _folded_forward(conv, bn, x, residual, act, image_norm) if ok else None
+        Fn.fusion("frozen_bn_folded", y is not None)
+        if y is not None:
+            return y
+    if image_norm is not None:
+        y0 = conv.forward_image(x, *image_norm)
+        if y0 is None:
+            y0 = conv(Fn.to_nhwc(x, image_norm[0], image_norm[1], pad_to=4), **conv_kwargs)
+    else:
+        y0 = conv(x, **conv_kwargs)
+    return bn(y0, residual=residual, act=act, drop_p=drop_p, grad_box=bn_grad_box)

@@ -5,7 +5,7 @@ import torch
 from torch import nn
 
 from .. import functional as Fn
-from .layers import Conv2d, BatchNorm2d
+from .layers import Conv2d, BatchNorm2d, conv_bn
 
 
 class ASPPConv(nn.Sequential):
@@ -14,7 +14,7 @@ class ASPPConv(nn.Sequential):
                          BatchNorm2d(out_channels), nn.ReLU())
 
     def forward(self, x, grad_box=None):
-        return self[1](self[0](x, grad_box=grad_box), act="relu")
+        return conv_bn(self[0], self[1], x, act="relu", grad_box=grad_box)
 
 
 class ASPPPooling(nn.Sequential):
@@ -25,7 +25,7 @@ class ASPPPooling(nn.Sequential):
     def forward(self, x):
         size = (x.shape[1], x.shape[2])
         g = Fn.GlobalAvgPoolFn.apply(x)
-        g = self[2](self[1](g), act="relu")
+        g = conv_bn(self[1], self[2], g, act="relu")
         return Fn.ResizeFn.apply(g, size, False)
 
 
@@ -53,13 +53,13 @@ class ASPP(nn.Module):
             xs = Fn.FanoutFn.apply(x, box, len(branches))
         else:
             box, xs = None, [x] * len(branches)
-        res = [self.convs[0][1](self.convs[0][0](xs[0], grad_box=box), act="relu")]
+        res = [conv_bn(self.convs[0][0], self.convs[0][1], xs[0], act="relu", grad_box=box)]
         for conv, xi in zip(branches[1:], xs[1:]):
             res.append(conv(xi, grad_box=box) if isinstance(conv, ASPPConv) else conv(xi))
         cat = Fn.ConcatFn.apply(*res)
         drop = self.project[3]
         p = drop.p if (drop.training and self.training) else 0.0
-        return self.project[1](self.project[0](cat), act="relu", drop_p=p)
+        return conv_bn(self.project[0], self.project[1], cat, act="relu", drop_p=p)
 
 
 class SelfAttention(nn.Module):

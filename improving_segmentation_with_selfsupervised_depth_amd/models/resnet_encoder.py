@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from .. import functional as Fn
-from .layers import Conv2d, BatchNorm2d
+from .layers import Conv2d, BatchNorm2d, conv_bn
 
 
 class BasicBlock(nn.Module):
@@ -37,13 +37,13 @@ class BasicBlock(nn.Module):
             # identity skip: conv1's data-gradient lands on the skip-path gradient inside its kernel (Fn.SplitFn)
             box = {}
             xm, xs = Fn.SplitFn.apply(x, box)
-            o = self.bn1(self.conv1(xm, grad_box=box), act="relu")
-            return self.bn2(self.conv2(o), residual=xs, act="relu", grad_box=box)
+            o = conv_bn(self.conv1, self.bn1, xm, act="relu", grad_box=box)
+            return conv_bn(self.conv2, self.bn2, o, residual=xs, act="relu", bn_grad_box=box)
         if self.downsample is not None and x_ds is None and x.requires_grad:
             (x, x_ds), box = Fn.fan_feature(x, 0, 2)       # conv1 and the downsample convolution read x: one summed gradient
-        idt = x if self.downsample is None else self.downsample[1](self.downsample[0](x if x_ds is None else x_ds, grad_box=box))
-        o = self.bn1(self.conv1(x, grad_box=box), act="relu")
-        return self.bn2(self.conv2(o), residual=idt, act="relu")
+        idt = x if self.downsample is None else conv_bn(self.downsample[0], self.downsample[1], x if x_ds is None else x_ds, grad_box=box)
+        o = conv_bn(self.conv1, self.bn1, x, act="relu", grad_box=box)
+        return conv_bn(self.conv2, self.bn2, o, residual=idt, act="relu")
 
 
 class Bottleneck(nn.Module):
@@ -65,15 +65,15 @@ class Bottleneck(nn.Module):
         if self.downsample is None and x.requires_grad:
             box = {}
             xm, xs = Fn.SplitFn.apply(x, box)
-            o = self.bn1(self.conv1(xm, grad_box=box), act="relu")
-            o = self.bn2(self.conv2(o), act="relu")
-            return self.bn3(self.conv3(o), residual=xs, act="relu", grad_box=box)
+            o = conv_bn(self.conv1, self.bn1, xm, act="relu", grad_box=box)
+            o = conv_bn(self.conv2, self.bn2, o, act="relu")
+            return conv_bn(self.conv3, self.bn3, o, residual=xs, act="relu", bn_grad_box=box)
         if self.downsample is not None and x_ds is None and x.requires_grad:
             (x, x_ds), box = Fn.fan_feature(x, 0, 2)
-        idt = x if self.downsample is None else self.downsample[1](self.downsample[0](x if x_ds is None else x_ds, grad_box=box))
-        o = self.bn1(self.conv1(x, grad_box=box), act="relu")
-        o = self.bn2(self.conv2(o), act="relu")
-        return self.bn3(self.conv3(o), residual=idt, act="relu")
+        idt = x if self.downsample is None else conv_bn(self.downsample[0], self.downsample[1], x if x_ds is None else x_ds, grad_box=box)
+        o = conv_bn(self.conv1, self.bn1, x, act="relu", grad_box=box)
+        o = conv_bn(self.conv2, self.bn2, o, act="relu")
+        return conv_bn(self.conv3, self.bn3, o, residual=idt, act="relu")
 
 
 class ResNet(nn.Module):
@@ -177,10 +177,8 @@ class ResnetEncoder(nn.Module):
         # tile loads are 16-byte gathers (K = 49*4 instead of 49*3, but 2.5x faster than the scalar gather)
         # -- or, for the reference's own stem geometry, written with the zero border of the 7x7 window around it and
         # convolved by the dedicated stem kernel (Conv2d.forward_image)
-        y0 = e.conv1.forward_image(input_image, 0.45, 0.225)
-        if y0 is None:
-            y0 = e.conv1(Fn.to_nhwc(input_image, 0.45, 0.225, pad_to=4))
-        f0 = e.bn1(y0, act="relu")
+        # (layers.conv_bn: that pair, or one launch when bn1 is frozen and folded)
+        f0 = conv_bn(e.conv1, e.bn1, input_image, act="relu", image_norm=(0.45, 0.225))
         feats = [f0]
         # The features are read again as the skip sources of ``self.skip_consumers`` decoders (set by the model glue): every
         # feature becomes a set of Fn.FanoutFn views -- the ones for the next stage are used here, the decoders fetch theirs with

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 16
+#define SEGSDE_ABI_VERSION 17
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -108,6 +108,18 @@ int segsde_conv2d_forward_stats(const segsde_conv_desc* d, const float* x0, cons
 int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const float* x0, const float* x1, const float* wpack,
                                 const float* bias, float* y, float* y2, double* stats, const float* act_out, int act_ld,
                                 int act_kind, void* stream);
+/* Forward launch with a residual operand: y = act((conv + bias) + res), in that association, d->act any SEGSDE_ACT_*; res is
+ * [B,Ho,Wo,Cout] with pixel pitch ldr.  With the weights and bias of segsde_bn_fold it replaces the conv -> frozen BatchNorm ->
+ * (+ identity) -> ReLU tail of torchvision's Bottleneck / BasicBlock (reached from models/resnet_encoder.py:93-99) in no-grad
+ * forward passes: the segsde_bn_apply pass over the convolution output (one read, one write) is not needed.  res == y with
+ * ldr == ldy (in place) is allowed -- every thread loads the residual values of exactly the elements it stores, before it stores
+ * them; any other overlap of the two tensors returns SEGSDE_ERR_SHAPE.  The epilogue is shared by every loop of the kernel, so
+ * every d->compute mode the launch takes (fp32, fp16, split bf16) carries the residual.  One destination only: a second
+ * destination (nsplit / ldy2), sum2x2, in_div > 1, accumulate, SEGSDE_PAD_REFLECT_ADJOINT, Cout == 1 and shapes without the
+ * 16-byte epilogue (Cout, ldy, ldr multiples of 4, y and res 16-byte aligned) return SEGSDE_ERR_UNSUPPORTED (the caller then runs
+ * segsde_conv2d_forward + segsde_bn_apply).  No statistics partials: a BatchNorm that is folded has none to take. */
+int segsde_conv2d_forward_residual(const segsde_conv_desc* d, const float* x0, const float* x1, const float* wpack,
+                                   const float* bias, const float* res, int ldr, float* y, void* stream);
 
 /* dW (OIHW, the state_dict layout) of the convolution described by d, given dy [B,Ho,Wo,Cout] (pitch lddy). */
 size_t segsde_conv2d_wgrad_workspace(const segsde_conv_desc* d);
@@ -149,6 +161,11 @@ int segsde_stem_pack(const float* w_oihw, int Cout, int C, int cp, float* wstem,
 long segsde_stem7x7_stats_rows(int B, int Hp, int Wp, int cp, int Cout);
 int segsde_stem7x7_forward(const float* xpad, int B, int Hp, int Wp, int cp, const float* wstem, int Cout, float* y, double* stats,
                            void* stream);
+/* The stem launch with a bias and an activation, y = act(conv + bias[n]) (bias nullable, act SEGSDE_ACT_*): conv1 -> frozen bn1 ->
+ * ReLU of the stem (models/resnet_encoder.py:93-95) as one launch on the weights and bias of segsde_bn_fold; replaces
+ * segsde_stem7x7_forward + segsde_bn_apply in no-grad forward passes.  No statistics partials. */
+int segsde_stem7x7_forward_bias_act(const float* xpad, int B, int Hp, int Wp, int cp, const float* wstem, int Cout,
+                                    const float* bias, int act, float* y, void* stream);
 size_t segsde_stem7x7_wgrad_workspace(int B, int Hp, int Wp, int cp, int Cout);
 int segsde_stem7x7_wgrad(const float* xpad, int B, int Hp, int Wp, int cp, const float* dy, int lddy, int Cout, int C,
                          float* dw_oihw, float* workspace, size_t workspace_bytes, void* stream);
@@ -188,6 +205,21 @@ int segsde_bn_stats(const float* x, int ldx, long M, int C, float* mean, float* 
 /* Eval mode: mean = running_mean, invstd = 1/sqrt(running_var + eps). */
 int segsde_bn_eval_stats(const float* running_mean, const float* running_var, int C, float eps, float* mean,
                          float* invstd, void* stream);
+/* A frozen (eval-mode) BatchNorm folded into the convolution in front of it, for many (convolution, BatchNorm) pairs in one
+ * launch:  w_out[o,i,kh,kw] = w[o,i,kh,kw] * s[o],  b_out[o] = beta[o] - mean[o] * s[o] (+ cb[o] * s[o]),  s[o] = gamma[o] * invstd[o]
+ * with invstd[o] = 1/sqrt(var[o] + eps) -- the expression of segsde_bn_eval_stats, bit for bit; plain fp32 in the order written.
+ * bn(conv(x, w) + cb) == conv(x, w_out) + b_out up to fp32 re-association: the conv -> bn pairs of models/resnet_encoder.py and
+ * models/model_parts.py (ASPP) in eval mode then need no segsde_bn_eval_stats + segsde_bn_apply pass.  cb (the convolution's own
+ * bias), gamma and beta are nullable (no bias; affine=False: 1 and 0); any O, I, KH, KW.  jobs_device: njobs + 1 entries in
+ * DEVICE memory, job j runs on blocks [block0, next entry's block0) of the launch (at least one; one element per thread and
+ * trip), the last entry is a sentinel whose block0 is total_blocks. */
+typedef struct segsde_bn_fold_job {
+  const float* w; const float* cb; const float* gamma; const float* beta; const float* mean; const float* var;
+  float* w_out; float* b_out;
+  float eps;
+  int O, I, KH, KW, block0, reserved;
+} segsde_bn_fold_job;
+int segsde_bn_fold(const segsde_bn_fold_job* jobs_device, int njobs, int total_blocks, void* stream);
 /* y = dropout(act(gamma*(x-mean)*invstd + beta + residual)); dropout keeps with prob 1-p and scales by 1/(1-p)
  * (nn.Dropout(0.5) in ASPP.project, models/model_parts.py:21-25), mask = hash(seed, element). */
 int segsde_bn_apply(const float* x, int ldx, long M, int C, const float* mean, const float* invstd, const float* gamma,
