@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -174,6 +174,10 @@ _SIGS = {
     "segsde_minmax_normalize_workspace": (c_size_t, [c_int, c_long]),
     "segsde_minmax_normalize": (c_int, [P, c_int, c_long, P, P, P, P, c_size_t, P]),
     "segsde_disp_to_depth": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P]),
+    "segsde_batchprep_crop": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P]),
+    "segsde_batchprep_pyramid_level": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
+    "segsde_batchprep_labels": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, c_int64, c_int, P, P, P]),
+    "segsde_batchprep_plane": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -1,0 +1,287 @@
+// Device side of the data loader (loader/sequence_segmentation_loader.py:203-342 plus collation): decoded uint8 frames in,
+// the training `inputs` tensors out.  Everything is integer arithmetic or one correctly rounded division, so every output is
+// bit-identical to what PIL + ToTensor produce on the host:
+//   crop_rgb_kernel   get_color's flip, random_crop's crop, ToTensor            (:145-150, :259-267, :319)
+//   pyramid_kernel    transforms.Resize(..., Image.ANTIALIAS) by exactly 2, chained level to level, + ToTensor  (:308-309, :319)
+//   labels_kernel     crop + flip + encode_segmap (a 256-entry table) + the one-hot planes              (:227-248, :324-327)
+//   plane_kernel      crop + flip + ToTensor of the one-channel pseudo_depth image                      (:272-273, :329-330)
+// The 8-bit level images stay planar ([planes][H][W], one plane per sample and channel): the pyramid reads them with 16-byte
+// loads and ToTensor's CHW float planes are written next to them from the same registers.
+#include "segsde_common.h"
+
+namespace {
+#define ST(s) static_cast<hipStream_t>(s)
+typedef unsigned bp_u32x4 __attribute__((ext_vector_type(4)));
+
+// crop offsets are device data: an offset outside [0, frame - crop] is pulled back inside, never followed out of the tensor
+__device__ __forceinline__ int crop_origin(const int* crop_xy, int i, int room) {
+  const int v = crop_xy ? crop_xy[i] : 0;
+  return v < 0 ? 0 : (v > room ? room : v);
+}
+// ToTensor: uint8 / 255 in fp32, correctly rounded (Markstein's two-fma division by a constant, as div_by<C> of loss.hip; the
+// 256 possible inputs are compared with the IEEE quotient in tests/test_device_batch_emu.py and on the GPU)
+__device__ __forceinline__ float unit_from_u8(unsigned v) {
+  constexpr float rc = 1.f / 255.f;
+  const float x = (float)v, q = x * rc;
+  return __builtin_fmaf(__builtin_fmaf(-255.f, q, x), rc, q);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// crop + flip + ToTensor of an HWC frame.  One wave owns CROP_SEG output pixels of one row: their 3 * CROP_SEG source bytes
+// are contiguous whether or not the sample is flipped (a flip only reverses the pixel order), so the wave fetches them as
+// 16-byte aligned chunks into LDS (whatever the crop offset makes of the alignment) and every lane then turns four
+// neighbouring pixels into one 16-byte store per float plane and one 4-byte store per uint8 plane.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int CROP_SEG = 256;                       // pixels per wave
+constexpr int CROP_LDS = 3 * CROP_SEG + 32;         // + the chunk alignment slack on both sides
+
+__global__ __launch_bounds__(256) void crop_rgb_kernel(const uint8_t* frames, long frame_bytes, int H, int W, const int* crop_xy,
+                                                       const uint8_t* flip, int ch, int cw, uint8_t* u8, float* f32, int vec) {
+  SEGSDE_SMEM;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  uint8_t* sm = segsde_smem + wv * CROP_LDS;
+  const int b = blockIdx.z, y = blockIdx.y * 4 + wv, x0 = blockIdx.x * CROP_SEG;
+  const int x1 = crop_origin(crop_xy, 2 * b, W - cw), y1 = crop_origin(crop_xy, 2 * b + 1, H - ch);
+  const bool fl = flip && flip[b];
+  const int n = cw - x0 < CROP_SEG ? cw - x0 : CROP_SEG;
+  const bool live = y < ch;
+  int skew = 0;
+  if (live) {
+    // flip, then crop: output x reads source column W - 1 - (x1 + x) of a flipped sample
+    const int sx = fl ? W - (x1 + x0 + n) : x1 + x0;
+    const long first = (((long)b * H + y1 + y) * W + sx) * 3, last = first + 3L * n;      // byte range inside `frames`
+    skew = (int)(reinterpret_cast<uintptr_t>(frames + first) & 15);
+    const int chunks = (skew + 3 * n + 15) >> 4;                                           // <= 49
+    if (lane < chunks) {
+      const long at = first - skew + 16L * lane;
+      bp_u32x4 v;
+      if (at >= 0 && at + 16 <= frame_bytes) {
+        v = *reinterpret_cast<const bp_u32x4*>(frames + at);
+      } else {                                    // the chunk sticks out of the tensor: only the bytes of this segment are read
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        for (int i = 0; i < 16; ++i)
+          if (at + i >= first && at + i < last) w[i >> 2] |= (unsigned)frames[at + i] << (8 * (i & 3));
+        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+      }
+      *reinterpret_cast<bp_u32x4*>(sm + 16 * lane) = v;
+    }
+  }
+  __syncthreads();
+  if (!live || 4 * lane >= n) return;
+  const uint8_t* px = sm + skew;
+  const long plane = (long)ch * cw, o = ((long)b * 3 * ch + y) * cw + x0 + 4 * lane;
+  if (vec) {                                      // cw % 4 == 0: whole groups of four
+    for (int c = 0; c < 3; ++c) {
+      unsigned q[4];
+      for (int k = 0; k < 4; ++k) {
+        const int i = 4 * lane + k;
+        q[k] = px[3 * (fl ? n - 1 - i : i) + c];
+      }
+      *reinterpret_cast<unsigned*>(u8 + o + c * plane) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+      *reinterpret_cast<float4*>(f32 + o + c * plane) =
+          make_float4(unit_from_u8(q[0]), unit_from_u8(q[1]), unit_from_u8(q[2]), unit_from_u8(q[3]));
+    }
+  } else {
+    for (int k = 0; k < 4 && 4 * lane + k < n; ++k) {
+      const int i = 4 * lane + k;
+      for (int c = 0; c < 3; ++c) {
+        const unsigned q = px[3 * (fl ? n - 1 - i : i) + c];
+        u8[o + k + c * plane] = (uint8_t)q;
+        f32[o + k + c * plane] = unit_from_u8(q);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// One pyramid level: Pillow's 8-bit resampler (Resample.c) for the Lanczos filter at an exact reduction by 2.
+//   pass 1 (horizontal), pass 2 (vertical), a uint8 image in between; per output  clip8((2^21 + sum_j k[j] * pix[j]) >> 22)
+//   with k[j] = (int)(w[j] * 2^22 +- 0.5), w = the normalised float64 window sinc(x) sinc(x / 3) of support 6.
+// Output xx reads the 12 source pixels 2 xx - 5 .. 2 xx + 6; windows cut by a border are renormalised by Pillow, so the first
+// three and the last three outputs of an axis have coefficient sets of their own.  The table comes from the host (float64,
+// Pillow's formula): per axis 7 rows x 12 taps, taps outside the image zero; output xx of an axis of n outputs uses row
+//   xx                     for xx < 3          (left border)
+//   R - (n - xx)           for xx >= n - 3     (right border; R = min(n, 7) rows are in use)
+//   3                      otherwise           (interior: every window whole, one set for all)
+// A block makes PYR_W x PYR_H outputs of one plane: source tile + halo into LDS (16-byte loads when the rows allow it),
+// horizontal pass LDS -> LDS (rounded and clipped to uint8, as Pillow's intermediate image is), vertical pass LDS -> global.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int PYR_W = 64, PYR_H = 16;                 // outputs per block (tests/device_batch_cases.py: case B spans several)
+constexpr int PYR_TAPS = 12, PYR_ROWS = 7;
+constexpr int PYR_SRC_ROWS = 2 * PYR_H + 10;          // 5 rows of halo above, 5 below (the 12-tap window of an even reduction)
+constexpr int PYR_SRC_PITCH = 2 * PYR_W + 32;         // tile column 0 = source column 2 * tx0 - 16: chunks stay 16-byte aligned
+constexpr int PYR_COEF_BYTES = 2 * PYR_ROWS * PYR_TAPS * 4;
+constexpr int PYR_SRC_BYTES = PYR_SRC_ROWS * PYR_SRC_PITCH;
+constexpr int PYR_MID_BYTES = PYR_SRC_ROWS * PYR_W;
+constexpr int PYR_LDS = PYR_COEF_BYTES + PYR_SRC_BYTES + PYR_MID_BYTES;
+static_assert(PYR_COEF_BYTES % 16 == 0 && PYR_SRC_BYTES % 16 == 0, "LDS regions stay 16-byte aligned");
+static_assert(PYR_W * PYR_H == 4 * 256, "vertical pass: four outputs per thread");
+
+__device__ __forceinline__ int pyr_row(int xx, int n) {
+  const int R = n < PYR_ROWS ? n : PYR_ROWS;
+  return xx < 3 ? xx : (xx >= n - 3 ? R - (n - xx) : 3);
+}
+__device__ __forceinline__ unsigned pyr_clip8(int acc) {
+  const int v = acc >> 22;                            // arithmetic shift: Pillow indexes its clip table with ss >> PRECISION_BITS
+  return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+__global__ __launch_bounds__(256) void pyramid_kernel(const uint8_t* src, int Hs, int Ws, const int* coef, int Hd, int Wd,
+                                                      uint8_t* u8, float* f32, int vec_in, int vec_out) {
+  SEGSDE_SMEM;
+  int* ck = reinterpret_cast<int*>(segsde_smem);                        // [2][7][12]: the y rows, then the x rows
+  uint8_t* ssrc = segsde_smem + PYR_COEF_BYTES;                          // [PYR_SRC_ROWS][PYR_SRC_PITCH]
+  uint8_t* smid = ssrc + PYR_SRC_BYTES;                                  // [PYR_SRC_ROWS][PYR_W]
+  const int t = threadIdx.x;
+  const int tx0 = blockIdx.x * PYR_W, ty0 = blockIdx.y * PYR_H;
+  const uint8_t* sp = src + (long)blockIdx.z * Hs * Ws;
+  if (t < 2 * PYR_ROWS * PYR_TAPS) ck[t] = coef[t];
+  const int sy0 = 2 * ty0 - 5, sx0 = 2 * tx0 - 16;
+  if (vec_in) {                                       // Ws % 16 == 0, aligned base: a chunk is inside the row or outside it
+    constexpr int CPR = PYR_SRC_PITCH / 16;
+    for (int e = t; e < PYR_SRC_ROWS * CPR; e += 256) {
+      const int r = e / CPR, j = e - r * CPR, sy = sy0 + r, c0 = sx0 + 16 * j;
+      bp_u32x4 v = {0u, 0u, 0u, 0u};
+      if (sy >= 0 && sy < Hs && c0 >= 0 && c0 + 16 <= Ws) v = *reinterpret_cast<const bp_u32x4*>(sp + (long)sy * Ws + c0);
+      *reinterpret_cast<bp_u32x4*>(ssrc + r * PYR_SRC_PITCH + 16 * j) = v;
+    }
+  } else {
+    for (int e = t; e < PYR_SRC_BYTES; e += 256) {
+      const int r = e / PYR_SRC_PITCH, c = e - r * PYR_SRC_PITCH, sy = sy0 + r, sx = sx0 + c;
+      ssrc[e] = (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) ? sp[(long)sy * Ws + sx] : (uint8_t)0;
+    }
+  }
+  __syncthreads();
+  // horizontal pass: an item is four neighbouring outputs of one tile row; their windows span 18 source bytes, fetched as
+  // the six dwords from tile column 8 g + 8 (output 4 g + k, tap j = tile column 2 (4 g + k) + 11 + j = byte 3 + 2 k + j)
+  const int* kx = ck + PYR_ROWS * PYR_TAPS;
+  for (int e = t; e < PYR_SRC_ROWS * (PYR_W / 4); e += 256) {
+    const int r = e / (PYR_W / 4), g = e - r * (PYR_W / 4);
+    const unsigned* row = reinterpret_cast<const unsigned*>(ssrc + r * PYR_SRC_PITCH + 8 * g + 8);
+    unsigned w[6];
+    for (int i = 0; i < 6; ++i) w[i] = row[i];
+    unsigned packed = 0u;
+    for (int k = 0; k < 4; ++k) {
+      const int xx = tx0 + 4 * g + k;
+      if (xx >= Wd) break;
+      const int* kr = kx + pyr_row(xx, Wd) * PYR_TAPS;
+      int acc = 1 << 21;
+      for (int j = 0; j < PYR_TAPS; ++j) {
+        const int i = 3 + 2 * k + j;
+        acc += kr[j] * (int)((w[i >> 2] >> (8 * (i & 3))) & 255u);
+      }
+      packed |= pyr_clip8(acc) << (8 * k);
+    }
+    *reinterpret_cast<unsigned*>(smid + r * PYR_W + 4 * g) = packed;
+  }
+  __syncthreads();
+  // vertical pass: thread = four neighbouring outputs of one row; output row yl reads the rows 2 yl .. 2 yl + 11 of the tile
+  const int g = t & 15, yl = t >> 4, yy = ty0 + yl, xx0 = tx0 + 4 * g;
+  if (yy >= Hd || xx0 >= Wd) return;
+  const int* kr = ck + pyr_row(yy, Hd) * PYR_TAPS;
+  int acc[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+  for (int j = 0; j < PYR_TAPS; ++j) {
+    const unsigned w = *reinterpret_cast<const unsigned*>(smid + (2 * yl + j) * PYR_W + 4 * g);
+    const int kj = kr[j];
+    for (int k = 0; k < 4; ++k) acc[k] += kj * (int)((w >> (8 * k)) & 255u);
+  }
+  unsigned q[4];
+  for (int k = 0; k < 4; ++k) q[k] = pyr_clip8(acc[k]);
+  const long o = ((long)blockIdx.z * Hd + yy) * Wd + xx0;
+  if (vec_out) {                                      // Wd % 4 == 0, aligned bases
+    *reinterpret_cast<unsigned*>(u8 + o) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+    *reinterpret_cast<float4*>(f32 + o) = make_float4(unit_from_u8(q[0]), unit_from_u8(q[1]), unit_from_u8(q[2]), unit_from_u8(q[3]));
+  } else {
+    for (int k = 0; k < 4 && xx0 + k < Wd; ++k) { u8[o + k] = (uint8_t)q[k]; f32[o + k] = unit_from_u8(q[k]); }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// one-channel maps: a thread per output pixel (the int64 / fp32 outputs are 8x / 4x the bytes of the uint8 input)
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long crop_src(int b, int y, int x, int H, int W, const int* crop_xy, const uint8_t* flip, int ch, int cw) {
+  const int x1 = crop_origin(crop_xy, 2 * b, W - cw), y1 = crop_origin(crop_xy, 2 * b + 1, H - ch);
+  const int sx = (flip && flip[b]) ? W - 1 - (x1 + x) : x1 + x;
+  return ((long)b * H + y1 + y) * W + sx;
+}
+__global__ __launch_bounds__(256) void labels_kernel(const uint8_t* lbl, int B, int H, int W, const int* crop_xy, const uint8_t* flip,
+                                                     int ch, int cw, const int64_t* lut, const uint8_t* is_labeled,
+                                                     int64_t ignore_index, int n_classes, int64_t* out, int64_t* onehot) {
+  const long HW = (long)ch * cw, total = (long)B * HW;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int b = (int)(e / HW);
+    const long p = e - b * HW;
+    const int y = (int)(p / cw), x = (int)(p - (long)y * cw);
+    const bool labeled = !is_labeled || is_labeled[b];
+    const int64_t v = labeled ? lut[lbl[crop_src(b, y, x, H, W, crop_xy, flip, ch, cw)]] : ignore_index;
+    out[e] = v;
+    if (onehot) {                                     // ignore pixels and unlabeled samples: every plane zero
+      int64_t* oh = onehot + (long)b * n_classes * HW + p;
+      for (int c = 0; c < n_classes; ++c) oh[c * HW] = (labeled && v == c) ? 1 : 0;
+    }
+  }
+}
+__global__ __launch_bounds__(256) void plane_kernel(const uint8_t* src, int B, int H, int W, const int* crop_xy, const uint8_t* flip,
+                                                    int ch, int cw, float* out) {
+  const long HW = (long)ch * cw, total = (long)B * HW;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int b = (int)(e / HW);
+    const long p = e - b * HW;
+    const int y = (int)(p / cw), x = (int)(p - (long)y * cw);
+    out[e] = unit_from_u8(src[crop_src(b, y, x, H, W, crop_xy, flip, ch, cw)]);
+  }
+}
+inline int flat_blocks(long n) { long nb = (n + 255) / 256; return (int)(nb < 1 ? 1 : (nb > 8192 ? 8192 : nb)); }
+inline bool crop_shape_ok(int B, int H, int W, int ch, int cw) {
+  return B > 0 && H > 0 && W > 0 && ch > 0 && cw > 0 && ch <= H && cw <= W && B <= 65535;
+}
+inline bool aligned16(const void* a, const void* b) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+}  // namespace
+
+extern "C" int segsde_batchprep_crop(const uint8_t* frames, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip,
+                                     int ch, int cw, uint8_t* u8_out, float* f32_out, void* stream) {
+  if (!frames || !u8_out || !f32_out) return SEGSDE_ERR_NULL;
+  if (!crop_shape_ok(B, H, W, ch, cw)) return SEGSDE_ERR_SHAPE;
+  if ((!crop_xy && (ch != H || cw != W)) || (long)segsde_cdiv(ch, 4) > 65535) return SEGSDE_ERR_SHAPE;
+  const int vec = (cw & 3) == 0 && aligned16(f32_out, nullptr) && (reinterpret_cast<uintptr_t>(u8_out) & 3) == 0;
+  hipLaunchKernelGGL(crop_rgb_kernel, dim3(segsde_cdiv(cw, CROP_SEG), segsde_cdiv(ch, 4), B), dim3(256), 4 * CROP_LDS, ST(stream),
+                     frames, (long)B * H * W * 3, H, W, crop_xy, flip, ch, cw, u8_out, f32_out, vec);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_batchprep_pyramid_level(const uint8_t* src, int planes, int Hs, int Ws, const int32_t* coef, int Hd, int Wd,
+                                              uint8_t* u8_out, float* f32_out, void* stream) {
+  if (!src || !coef || !u8_out || !f32_out) return SEGSDE_ERR_NULL;
+  if (planes <= 0 || planes > 65535 || Hd <= 0 || Wd <= 0 || Hs != 2 * Hd || Ws != 2 * Wd) return SEGSDE_ERR_SHAPE;
+  if (segsde_cdiv(Hd, PYR_H) > 65535) return SEGSDE_ERR_SHAPE;
+  const int vec_in = (Ws & 15) == 0 && aligned16(src, nullptr);
+  const int vec_out = (Wd & 3) == 0 && aligned16(f32_out, nullptr) && (reinterpret_cast<uintptr_t>(u8_out) & 3) == 0;
+  hipLaunchKernelGGL(pyramid_kernel, dim3(segsde_cdiv(Wd, PYR_W), segsde_cdiv(Hd, PYR_H), planes), dim3(256), PYR_LDS, ST(stream), src,
+                     Hs, Ws, coef, Hd, Wd, u8_out, f32_out, vec_in, vec_out);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_batchprep_labels(const uint8_t* lbl, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch,
+                                       int cw, const int64_t* lut, const uint8_t* is_labeled, int64_t ignore_index, int n_classes,
+                                       int64_t* lbl_out, int64_t* onehot_out, void* stream) {
+  if (!lbl || !lut || !lbl_out) return SEGSDE_ERR_NULL;
+  if (!crop_shape_ok(B, H, W, ch, cw) || (!crop_xy && (ch != H || cw != W)) || (onehot_out && n_classes <= 0)) return SEGSDE_ERR_SHAPE;
+  hipLaunchKernelGGL(labels_kernel, dim3(flat_blocks((long)B * ch * cw)), dim3(256), 0, ST(stream), lbl, B, H, W, crop_xy, flip, ch, cw,
+                     lut, is_labeled, ignore_index, n_classes, lbl_out, onehot_out);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_batchprep_plane(const uint8_t* src, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch,
+                                      int cw, float* out, void* stream) {
+  if (!src || !out) return SEGSDE_ERR_NULL;
+  if (!crop_shape_ok(B, H, W, ch, cw) || (!crop_xy && (ch != H || cw != W))) return SEGSDE_ERR_SHAPE;
+  hipLaunchKernelGGL(plane_kernel, dim3(flat_blocks((long)B * ch * cw)), dim3(256), 0, ST(stream), src, B, H, W, crop_xy, flip, ch, cw,
+                     out);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}

@@ -1870,3 +1870,91 @@ def confusion_update(hist, gt, pred=None, logits=None):
         check(_lib.lib().segsde_confusion_update(None, 0, 0, 0, _p(pred), _p(gt), B, HW, C, _p(hist), _stream(gt)),
               "confusion_update")
     return hist
+
+
+# ----------------------------------------------------------------------------------------------
+# device side of the data loader (csrc/batchprep.hip; loader/device_batch.py is the caller)
+# ----------------------------------------------------------------------------------------------
+def _u8(t, name):
+    if t.dtype != torch.uint8:
+        raise TypeError("%s must be uint8, got %s" % (name, t.dtype))
+    return t.contiguous()
+
+
+def _crop_args(B, crop_xy, flip):
+    if crop_xy is not None and (crop_xy.dtype != torch.int32 or tuple(crop_xy.shape) != (B, 2)):
+        raise TypeError("crop_xy must be int32 [B,2]")
+    if flip is not None and (flip.dtype != torch.uint8 or tuple(flip.shape) != (B,)):
+        raise TypeError("flip must be uint8 [B]")
+    return (None if crop_xy is None else crop_xy.contiguous()), (None if flip is None else flip.contiguous())
+
+
+def _out_like(t, shape, dtype, like, name):
+    """a caller's output buffer: exactly the tensor the kernel writes, or a fresh one"""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != like.device or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), like.device))
+    return t
+
+
+def batchprep_crop(frames, crop_xy, flip, ch, cw, u8_out=None, f32_out=None):
+    """frames [B,H,W,3] uint8 -> (uint8 [B,3,ch,cw], float32 [B,3,ch,cw] = u8 / 255); flip first, then crop"""
+    frames = _u8(frames, "frames")
+    B, H, W, C = frames.shape
+    if C != 3:
+        raise ValueError("frames must be [B,H,W,3]")
+    crop_xy, flip = _crop_args(B, crop_xy, flip)
+    u8_out = _out_like(u8_out, (B, 3, ch, cw), torch.uint8, frames, "u8_out")
+    f32_out = _out_like(f32_out, (B, 3, ch, cw), torch.float32, frames, "f32_out")
+    check(_lib.lib().segsde_batchprep_crop(_p(frames), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(u8_out), _p(f32_out),
+                                           _stream(frames)), "batchprep_crop")
+    return u8_out, f32_out
+
+
+def batchprep_pyramid_level(src, coef, u8_out=None, f32_out=None):
+    """src [...,Hs,Ws] uint8 planes -> the level below (exactly half in both directions), uint8 and float32; coef: int32 [2,7,12]
+    (loader/device_batch.lanczos_half_table)"""
+    src = _u8(src, "src")
+    Hs, Ws = src.shape[-2:]
+    if Hs % 2 or Ws % 2:
+        Hd, Wd = (Hs + 1) // 2, (Ws + 1) // 2          # the library rejects it (SEGSDE_ERR_SHAPE)
+    else:
+        Hd, Wd = Hs // 2, Ws // 2
+    lead = tuple(src.shape[:-2])
+    if coef.dtype != torch.int32 or tuple(coef.shape) != (2, 7, 12):
+        raise TypeError("coef must be int32 [2,7,12]")
+    u8_out = _out_like(u8_out, lead + (Hd, Wd), torch.uint8, src, "u8_out")
+    f32_out = _out_like(f32_out, lead + (Hd, Wd), torch.float32, src, "f32_out")
+    planes = src.numel() // (Hs * Ws)
+    check(_lib.lib().segsde_batchprep_pyramid_level(_p(src), planes, Hs, Ws, _p(coef.contiguous()), Hd, Wd,
+                                                    _p(u8_out), _p(f32_out), _stream(src)), "batchprep_pyramid_level")
+    return u8_out, f32_out
+
+
+def batchprep_labels(lbl, crop_xy, flip, ch, cw, lut, is_labeled=None, ignore_index=250, n_classes=0, want_onehot=False):
+    """lbl [B,H,W] uint8 -> int64 [B,ch,cw] through the 256-entry table `lut` (int64), and optionally the one-hot planes"""
+    lbl = _u8(lbl, "lbl")
+    B, H, W = lbl.shape
+    crop_xy, flip = _crop_args(B, crop_xy, flip)
+    if lut.dtype != torch.int64 or lut.numel() != 256:
+        raise TypeError("lut must be int64 [256]")
+    if is_labeled is not None and (is_labeled.dtype != torch.uint8 or tuple(is_labeled.shape) != (B,)):
+        raise TypeError("is_labeled must be uint8 [B]")
+    out = torch.empty((B, ch, cw), dtype=torch.int64, device=lbl.device)
+    onehot = torch.empty((B, n_classes, ch, cw), dtype=torch.int64, device=lbl.device) if want_onehot else None
+    check(_lib.lib().segsde_batchprep_labels(_p(lbl), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(lut.contiguous()),
+                                             _p(is_labeled), int(ignore_index), int(n_classes), _p(out), _p(onehot), _stream(lbl)),
+          "batchprep_labels")
+    return out, onehot
+
+
+def batchprep_plane(src, crop_xy, flip, ch, cw):
+    """src [B,H,W] uint8 -> float32 [B,1,ch,cw] = u8 / 255"""
+    src = _u8(src, "src")
+    B, H, W = src.shape
+    crop_xy, flip = _crop_args(B, crop_xy, flip)
+    out = torch.empty((B, 1, ch, cw), dtype=torch.float32, device=src.device)
+    check(_lib.lib().segsde_batchprep_plane(_p(src), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(out), _stream(src)),
+          "batchprep_plane")
+    return out

@@ -1,0 +1,213 @@
+"""The training ``inputs`` dict built on the GPU from decoded uint8 frames.
+
+The reference prepares every sample on the CPU (loader/sequence_segmentation_loader.py:203-342): flip and crop three PIL frames,
+three chained ``Image.ANTIALIAS`` resizes per frame, twelve ``ToTensor`` calls, ``encode_segmap``, ``K`` / ``inv_K`` for four
+scales.  With ``DeviceBatchBuilder`` a DataLoader worker only decodes and hands over uint8 arrays; one batched stage on the
+device (csrc/batchprep.hip) then produces exactly -- bit for bit -- what ``__getitem__`` plus collation produce.  This module is
+not part of the reference's import surface.
+
+Not covered: ``color_aug`` (torchvision's PIL ``ColorJitter``); ``("color_aug", f, 0)`` is ``("color", f, 0)``, as in the reference
+whenever colour augmentation is off (``cityscapes_joint.yml``).  There is no CPU path: without the HIP library every call raises.
+"""
+import math
+import random
+
+import numpy as np
+import torch
+
+from .. import hipops as H
+
+_PRECISION_BITS = 32 - 8 - 2          # Pillow, Resample.c
+_TAPS, _ROWS = 12, 7
+
+
+def _lanczos(x):
+    def sinc(v):
+        return 1.0 if v == 0.0 else math.sin(math.pi * v) / (math.pi * v)
+    return sinc(x) * sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0
+
+
+def _pillow_window(xx, n_out):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for output ``xx`` of an axis reduced from 2 * n_out to n_out pixels with
+    the Lanczos filter: (first source pixel, fixed-point weights).  Float64 throughout, the same operations in the same order."""
+    in_size = 2 * n_out
+    scale = in_size / n_out
+    filterscale = max(scale, 1.0)
+    support = 3.0 * filterscale
+    center = (xx + 0.5) * scale
+    ss = 1.0 / filterscale
+    xmin = max(int(center - support + 0.5), 0)
+    xmax = min(int(center + support + 0.5), in_size) - xmin
+    w = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+    ww = 0.0
+    for v in w:
+        ww += v
+    if ww != 0.0:
+        w = [v / ww for v in w]
+    one = float(1 << _PRECISION_BITS)
+    return xmin, [int(v * one - 0.5) if v < 0 else int(v * one + 0.5) for v in w]
+
+
+def lanczos_half_rows(n_out):
+    """The coefficient rows of one axis as segsde_batchprep_pyramid_level reads them: int32 [7, 12]; tap j of output xx weighs
+    source pixel 2 xx - 5 + j (zero outside the image).  Rows 0..2: the first three outputs; the last three rows in use (of
+    min(n_out, 7)): the last three outputs; row 3: every interior output (whole windows are all alike)."""
+    rows = np.zeros((_ROWS, _TAPS), dtype=np.int32)
+    used = min(n_out, _ROWS)
+    for r in range(used):
+        xx = r if (r <= 3 or n_out < _ROWS) else n_out - (used - r)
+        xmin, k = _pillow_window(xx, n_out)
+        first = xmin - (2 * xx - 5)
+        assert first >= 0 and first + len(k) <= _TAPS
+        rows[r, first:first + len(k)] = k
+    return rows
+
+
+def lanczos_half_table(h_out, w_out):
+    """int32 [2, 7, 12]: the rows of the y axis, then of the x axis"""
+    return np.stack([lanczos_half_rows(h_out), lanczos_half_rows(w_out)])
+
+
+class DeviceBatchBuilder:
+    """``builder(frames, lbl=..., ...)`` -> the dict a batch of ``SequenceSegmentationLoader.__getitem__`` collates to.
+
+    ``random_horizontal_flip``: a positive probability configures the flip (the reference's
+    ``augmentations["random_horizontal_flip"]``); 0.0 means the key is absent, and no flip coin is drawn."""
+
+    def __init__(self, height, width, crop_h=None, crop_w=None, num_scales=4, frame_idxs=(0, -1, 1),
+                 intrinsics=(2262.52, 2265.3017905988554, 1096.98, 513.137), full_res_shape=(2048, 1024), label_lut=None,
+                 n_classes=None, ignore_index=250, load_onehot=False, is_train=True, random_horizontal_flip=0.0):
+        self.height, self.width = int(height), int(width)
+        self.is_train = bool(is_train)
+        if crop_h is None or crop_w is None or not self.is_train:          # sequence_segmentation_loader.py:81-86
+            self.crop_h, self.crop_w = self.height, self.width
+        else:
+            self.crop_h, self.crop_w = int(crop_h), int(crop_w)
+        if self.crop_h > self.height or self.crop_w > self.width:
+            raise ValueError("crop %dx%d larger than the %dx%d frames" % (self.crop_h, self.crop_w, self.height, self.width))
+        self.num_scales = int(num_scales)
+        self.frame_idxs = tuple(frame_idxs)
+        self.fx, self.fy, self.u0, self.v0 = intrinsics
+        self.full_res_shape = tuple(full_res_shape)
+        self.n_classes = n_classes
+        self.ignore_index = int(ignore_index)
+        self.load_onehot = bool(load_onehot)
+        if self.load_onehot and not n_classes:
+            raise ValueError("load_onehot needs n_classes")
+        self.random_horizontal_flip = float(random_horizontal_flip or 0.0)
+        self.label_lut = None if label_lut is None else np.asarray(label_lut).astype(np.int64).reshape(256)
+        self.level_sizes = [(self.crop_h, self.crop_w)]
+        for _ in range(1, self.num_scales):
+            h, w = self.level_sizes[-1]
+            self.level_sizes.append((h // 2, w // 2))       # an odd level is rejected by the kernel when it is reached
+        if min(self.level_sizes[-1]) < 1:
+            raise ValueError("%d scales do not fit a %dx%d crop" % (self.num_scales, self.crop_h, self.crop_w))
+        self._tables = [None] + [lanczos_half_table(*self.level_sizes[s]) for s in range(1, self.num_scales)]
+        self._dev = {}
+
+    # ---- host side -------------------------------------------------------------------------------------------------
+    def draw(self, batch_size):
+        """Crop offsets (int32 [B,2] = x1, y1) and flips (bool [B]) from Python's ``random`` in the reference's order per sample
+        (sequence_segmentation_loader.py:210-212, 259-260): the colour-augmentation coin (drawn whenever ``is_train``; its
+        result is unused here), the flip coin if a flip is configured, ``randint`` for x1, then for y1.  With ``is_train=False``
+        no coin is drawn and both ``randint`` calls are ``randint(0, 0)``, which still advance the generator as in the reference."""
+        crops = np.zeros((batch_size, 2), dtype=np.int32)
+        flips = np.zeros((batch_size,), dtype=np.bool_)
+        for b in range(batch_size):
+            if self.is_train:
+                random.random()
+            if self.is_train and self.random_horizontal_flip > 0.0:
+                flips[b] = random.random() < self.random_horizontal_flip
+            crops[b, 0] = random.randint(0, self.width - self.crop_w)
+            crops[b, 1] = random.randint(0, self.height - self.crop_h)
+        return crops, flips
+
+    def get_K(self, u_offset, v_offset, do_flip):
+        """the reference's get_K (:332-342), including its flip of v0"""
+        u0, v0 = self.u0, self.v0
+        if do_flip:
+            u0 = self.full_res_shape[0] - u0
+            v0 = self.full_res_shape[1] - v0
+        return np.array([[self.fx, 0, u0 - u_offset, 0],
+                         [0, self.fy, v0 - v_offset, 0],
+                         [0, 0, 1, 0],
+                         [0, 0, 0, 1]], dtype=np.float32)
+
+    def intrinsics(self, crops, flips):
+        """float32 [2, num_scales, B, 4, 4]: K and inv_K of every scale by the reference's numpy expressions (:277-286)"""
+        B = len(crops)
+        out = np.empty((2, self.num_scales, B, 4, 4), dtype=np.float32)
+        for b in range(B):
+            for scale in range(self.num_scales):
+                K = self.get_K(int(crops[b][0]), int(crops[b][1]), bool(flips[b]))
+                K[0, :] /= (2 ** scale)
+                K[1, :] /= (2 ** scale)
+                out[0, scale, b] = K
+                out[1, scale, b] = np.linalg.pinv(K)
+        return out
+
+    # ---- device side -----------------------------------------------------------------------------------------------
+    def _cached(self, key, device, make):
+        k = (key, str(device))
+        if k not in self._dev:
+            self._dev[k] = make().to(device)
+        return self._dev[k]
+
+    def colors(self, frames, crop_d, flip_d, inputs):
+        """the colour pyramid of every frame: one crop launch per frame, one launch per level for all frames together"""
+        first = frames[self.frame_idxs[0]]
+        B, device = first.shape[0], first.device
+        F = len(self.frame_idxs)
+        u8 = torch.empty((F, B, 3, self.crop_h, self.crop_w), dtype=torch.uint8, device=device)
+        color = torch.empty((F, B, 3, self.crop_h, self.crop_w), dtype=torch.float32, device=device)
+        for i, f in enumerate(self.frame_idxs):
+            H.batchprep_crop(frames[f], crop_d, flip_d, self.crop_h, self.crop_w, u8_out=u8[i], f32_out=color[i])
+            inputs[("color", f, 0)] = color[i]
+            inputs[("color_aug", f, 0)] = color[i]
+        for s in range(1, self.num_scales):
+            table = self._cached(("lanczos", s), device, lambda: torch.from_numpy(self._tables[s]))
+            u8, color = H.batchprep_pyramid_level(u8, table)
+            for i, f in enumerate(self.frame_idxs):
+                inputs[("color", f, s)] = color[i]
+        return inputs
+
+    def __call__(self, frames, lbl=None, pseudo_depth=None, is_labeled=None, idx=None, crops=None, flips=None):
+        first = frames[self.frame_idxs[0]]
+        B, device = first.shape[0], first.device
+        for f in self.frame_idxs:
+            if tuple(frames[f].shape) != (B, self.height, self.width, 3):
+                raise ValueError("frame %r: expected uint8 [%d,%d,%d,3], got %s" % (f, B, self.height, self.width, tuple(frames[f].shape)))
+        if crops is None and flips is None:        # also on the validation path: the reference's random_crop draws randint(0, 0) there
+            crops, flips = self.draw(B)
+        crops = np.zeros((B, 2), np.int32) if crops is None else np.asarray(torch.as_tensor(crops).cpu(), dtype=np.int32).reshape(B, 2)
+        flips = np.zeros((B,), np.bool_) if flips is None else np.asarray(torch.as_tensor(flips).cpu()).astype(np.bool_).reshape(B)
+        if (crops < 0).any() or (crops[:, 0] > self.width - self.crop_w).any() or (crops[:, 1] > self.height - self.crop_h).any():
+            raise ValueError("crop offsets outside the frame")
+        cropped = (self.crop_h, self.crop_w) != (self.height, self.width)
+        crop_d = torch.from_numpy(crops).to(device, non_blocking=True) if cropped else None
+        flip_d = torch.from_numpy(flips.astype(np.uint8)).to(device, non_blocking=True) if flips.any() else None
+
+        inputs = {}
+        self.colors(frames, crop_d, flip_d, inputs)
+
+        kk = torch.from_numpy(self.intrinsics(crops, flips)).to(device, non_blocking=True)     # one copy for all scales
+        for s in range(self.num_scales):
+            inputs[("K", s)], inputs[("inv_K", s)] = kk[0, s], kk[1, s]
+
+        labeled_d = None
+        if is_labeled is not None:
+            labeled_d = torch.as_tensor(is_labeled).to(device=device, dtype=torch.uint8)
+            inputs["is_labeled"] = labeled_d.bool()
+        if lbl is not None:
+            if self.label_lut is None:
+                raise ValueError("labels need label_lut (encode_segmap(arange(256)))")
+            lut = self._cached("lut", device, lambda: torch.from_numpy(self.label_lut))
+            inputs["lbl"], onehot = H.batchprep_labels(lbl, crop_d, flip_d, self.crop_h, self.crop_w, lut, labeled_d,
+                                                       self.ignore_index, self.n_classes or 0, self.load_onehot)
+            if self.load_onehot:
+                inputs["onehot_lbl"] = onehot
+        if pseudo_depth is not None:
+            inputs["pseudo_depth"] = H.batchprep_plane(pseudo_depth, crop_d, flip_d, self.crop_h, self.crop_w)
+        if idx is not None:
+            inputs["idx"] = torch.as_tensor(idx).to(device)
+        return inputs

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 17
+#define SEGSDE_ABI_VERSION 18
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -585,6 +585,37 @@ int segsde_color_jitter(const float* x, int B, long HW, const float* params, con
  * tmp: planes*H*W floats; taps are DEVICE arrays (normalised Gaussian weights, possibly truncated to their non-zero support). */
 int segsde_gaussian_blur(const float* x, int planes, int H, int W, const float* wy, int ny, const float* wx, int nx, float* tmp,
                          float* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ *
+ * Device side of the data loader: decoded uint8 frames -> the training `inputs` tensors            *
+ * (loader/sequence_segmentation_loader.py:203-342 + collation; csrc/batchprep.hip).  Bit-identical *
+ * to PIL + ToTensor: integer resampling, one correctly rounded division by 255.                    *
+ * crop_xy: DEVICE int32 [B][2] = {x1, y1} per sample (null: no crop, ch == H and cw == W required; *
+ * offsets outside the frame are clamped); flip: DEVICE uint8 [B] (null: none).  The flip comes     *
+ * BEFORE the crop (get_color :148-149, then random_crop :259-267).                                  *
+ * ------------------------------------------------------------------------------------------------ */
+/* frames [B,H,W,3] uint8 as decoded -> u8_out [B,3,ch,cw] (level 0 of the pyramid, planar) and f32_out [B,3,ch,cw] = u8 / 255
+ * (ToTensor, :319). */
+int segsde_batchprep_crop(const uint8_t* frames, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch, int cw,
+                          uint8_t* u8_out, float* f32_out, void* stream);
+/* One level of the colour pyramid (:308-309: transforms.Resize((h/2, w/2), Image.ANTIALIAS) of the level above): src
+ * [planes,Hs,Ws] uint8 -> u8_out [planes,Hd,Wd] and f32_out = u8 / 255, Pillow's 8-bit Lanczos resampler (horizontal pass,
+ * uint8 intermediate, vertical pass).  Exact halving only: SEGSDE_ERR_SHAPE unless Hs == 2 Hd and Ws == 2 Wd.
+ * coef: DEVICE int32 [2][7][12], the fixed-point windows of the y axis then of the x axis by Pillow's formula (computed on
+ * the host in float64): row r < 3 = output r, the last three rows in use (of min(n, 7)) = the last three outputs, row 3 =
+ * every interior output; tap j of output i weighs source pixel 2 i - 5 + j, taps outside the image are zero. */
+int segsde_batchprep_pyramid_level(const uint8_t* src, int planes, int Hs, int Ws, const int32_t* coef, int Hd, int Wd,
+                                   uint8_t* u8_out, float* f32_out, void* stream);
+/* lbl [B,H,W] uint8 label ids -> lbl_out [B,ch,cw] int64 = lut[id] (encode_segmap is a 256-entry table, DEVICE int64 [256];
+ * :324-327); samples whose is_labeled (DEVICE uint8 [B], null: all labeled) is 0 get ignore_index everywhere (:227-229).
+ * onehot_out (nullable) [B,n_classes,ch,cw] int64: plane c is 1 where the label is c; ignore pixels and unlabeled samples
+ * are zero in every plane (:236-248). */
+int segsde_batchprep_labels(const uint8_t* lbl, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch, int cw,
+                            const int64_t* lut, const uint8_t* is_labeled, int64_t ignore_index, int n_classes, int64_t* lbl_out,
+                            int64_t* onehot_out, void* stream);
+/* one-channel 8-bit image (pseudo_depth, :272-273, :329-330): src [B,H,W] uint8 -> out [B,1,ch,cw] = u8 / 255 */
+int segsde_batchprep_plane(const uint8_t* src, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch, int cw,
+                           float* out, void* stream);
 
 #ifdef __cplusplus
 }
