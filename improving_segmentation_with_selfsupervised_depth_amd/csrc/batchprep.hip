@@ -5,6 +5,8 @@
 //   pyramid_kernel    transforms.Resize(..., Image.ANTIALIAS) by exactly 2, chained level to level, + ToTensor  (:308-309, :319)
 //   labels_kernel     crop + flip + encode_segmap (a 256-entry table) + the one-hot planes              (:227-248, :324-327)
 //   plane_kernel      crop + flip + ToTensor of the one-channel pseudo_depth image                      (:272-273, :329-330)
+//   jitter_*_kernel   the PIL ColorJitter of color_aug (brightness / contrast / saturation / hue in a drawn order) + ToTensor
+//                     (:297-301, :318-322); Pillow's 8-bit arithmetic restated, fp32 and fp64 exactly where Pillow uses them
 // The 8-bit level images stay planar ([planes][H][W], one plane per sample and channel): the pyramid reads them with 16-byte
 // loads and ToTensor's CHW float planes are written next to them from the same registers.
 #include "segsde_common.h"
@@ -231,6 +233,174 @@ __global__ __launch_bounds__(256) void plane_kernel(const uint8_t* src, int B, i
     out[e] = unit_from_u8(src[crop_src(b, y, x, H, W, crop_xy, flip, ch, cw)]);
   }
 }
+// ---------------------------------------------------------------------------------------------------------------------
+// color_aug: torchvision's PIL ColorJitter on the level-0 crop.  Four operations, applied in the sample's drawn order with an
+// 8-bit image between every two of them; every pixel is independent except for contrast, whose degenerate image is the mean L
+// of the image AS IT STANDS when contrast's turn comes.  So: jitter_stats_kernel runs the operations in front of contrast and
+// sums L (integer atomics: the sum does not depend on the order of the additions), jitter_apply_kernel runs them again from
+// the source bytes, forms the mean and goes on.  No intermediate image is stored.
+//   ImageEnhance.* end in Image.blend(degenerate, image, alpha): fp32  t = d + alpha * (x - d), truncated; clipped to 0..255
+//   only when alpha is outside [0, 1] (inside, t cannot leave the range).  Degenerates: 0 (brightness), the image's mean L
+//   (contrast), the pixel's own L (saturation).  L = (19595 r + 38470 g + 7471 b + 0x8000) >> 16.
+//   hue: RGB -> HSV (8 bit each), H += shift mod 256, HSV -> RGB; Pillow computes these in float with some subexpressions in
+//   double, and the results depend on which -- the types below are Pillow's.  No product-sum here may become an fma.
+// The operation id only selects a switch case and nothing is indexed with it, so a corrupt `order` table cannot lead a read
+// out of range (the Python layer rejects a row that is no permutation before it is uploaded).
+// ---------------------------------------------------------------------------------------------------------------------
+enum { JIT_BRIGHTNESS = 0, JIT_CONTRAST = 1, JIT_SATURATION = 2, JIT_HUE = 3 };
+constexpr int JIT_PX = 4;                             // pixels per thread: one dword per uint8 plane, one float4 per float plane
+
+struct jit_rgb { int r, g, b; };
+
+__device__ __forceinline__ int jit_luma(const jit_rgb& p) { return (19595 * p.r + 38470 * p.g + 7471 * p.b + 0x8000) >> 16; }
+__device__ __forceinline__ int jit_blend(int d, int x, float alpha, bool clip) {
+#pragma clang fp contract(off)
+  const float t = (float)d + alpha * (float)(x - d);
+  if (clip) return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
+  return (int)t;
+}
+__device__ __forceinline__ jit_rgb jit_blend3(int dr, int dg, int db, const jit_rgb& p, float alpha) {
+  const bool clip = !(alpha >= 0.f && alpha <= 1.f);
+  return jit_rgb{jit_blend(dr, p.r, alpha, clip), jit_blend(dg, p.g, alpha, clip), jit_blend(db, p.b, alpha, clip)};
+}
+__device__ __forceinline__ int jit_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+// round half away from zero of a non-negative double, then the clip to 0..255
+__device__ __forceinline__ int jit_round8(double x) {
+  const double fl = floor(x);
+  return jit_clip8((int)fl + ((x - fl) >= 0.5 ? 1 : 0));
+}
+__device__ __forceinline__ jit_rgb jit_hue(const jit_rgb& p, int shift) {
+#pragma clang fp contract(off)
+  const int mx = p.r > p.g ? (p.r > p.b ? p.r : p.b) : (p.g > p.b ? p.g : p.b);
+  const int mn = p.r < p.g ? (p.r < p.b ? p.r : p.b) : (p.g < p.b ? p.g : p.b);
+  int H = 0, S = 0;
+  const int V = mx;
+  if (mx != mn) {
+    const float cr = (float)(mx - mn);
+    const float s = cr / (float)mx;
+    const float rc = (float)(mx - p.r) / cr, gc = (float)(mx - p.g) / cr, bc = (float)(mx - p.b) / cr;
+    float h;
+    if (p.r == mx) h = bc - gc;
+    else if (p.g == mx) h = (float)((2.0 + (double)rc) - (double)bc);
+    else h = (float)((4.0 + (double)gc) - (double)rc);
+    const double u = (double)h / 6.0 + 1.0;           // in (5/6, 11/6): fmod(u, 1.0) is u or the exact difference u - 1
+    const float hf = (float)(u >= 1.0 ? u - 1.0 : u);
+    H = jit_clip8((int)((double)hf * 255.0));
+    S = jit_clip8((int)((double)s * 255.0));
+  }
+  H = (H + shift) & 255;
+  if (S == 0) return jit_rgb{V, V, V};
+  const double x = (double)H * 6.0 / 255.0;
+  const double fi = floor(x);
+  const float f = (float)(x - fi);
+  const float fs = (float)((double)S / 255.0);
+  const double dv = (double)V, dfs = (double)fs, df = (double)f;
+  const int pp = jit_round8(dv * (1.0 - dfs));
+  const int q = jit_round8(dv * (1.0 - dfs * df));
+  const int t = jit_round8(dv * (1.0 - dfs * (1.0 - df)));
+  switch ((int)fi % 6) {
+    case 0: return jit_rgb{V, t, pp};
+    case 1: return jit_rgb{q, V, pp};
+    case 2: return jit_rgb{pp, V, t};
+    case 3: return jit_rgb{pp, q, V};
+    case 4: return jit_rgb{t, pp, V};
+    default: return jit_rgb{V, pp, q};
+  }
+}
+// the sample's tables, read once per thread (wave-uniform: scalar loads)
+struct jit_params { float alpha[3]; int shift; unsigned order, ops; };      // order: four 2-bit operation ids, first in the low bits
+__device__ __forceinline__ jit_params jit_load(int b, const float* alpha, const int* hue_shift, const uint8_t* order, int ops) {
+  jit_params P;
+  P.ops = (unsigned)ops;
+  for (int i = 0; i < 3; ++i) P.alpha[i] = alpha[3 * b + i];
+  P.shift = hue_shift[b] & 255;
+  P.order = 0u;
+  for (int i = 0; i < 4; ++i) P.order |= (unsigned)(order[4 * b + i] & 3) << (2 * i);
+  return P;
+}
+// the operations at positions [from, 4) of the order that the mask `ops` (bit = operation id) enables, stopping in front of
+// contrast when `mean` < 0; returns the position it stopped at (4: all done)
+__device__ __forceinline__ int jit_run(jit_rgb& p, const jit_params& P, int from, int mean) {
+  for (int i = from; i < 4; ++i) {
+    const unsigned op = (P.order >> (2 * i)) & 3u;
+    if (!((P.ops >> op) & 1u)) continue;
+    switch (op) {
+      case JIT_BRIGHTNESS: p = jit_blend3(0, 0, 0, p, P.alpha[0]); break;
+      case JIT_CONTRAST:
+        if (mean < 0) return i;
+        p = jit_blend3(mean, mean, mean, p, P.alpha[1]);
+        break;
+      case JIT_SATURATION: { const int l = jit_luma(p); p = jit_blend3(l, l, l, p, P.alpha[2]); break; }
+      default: p = jit_hue(p, P.shift); break;
+    }
+  }
+  return 4;
+}
+__device__ __forceinline__ void jit_fetch(const uint8_t* img, long hw, long at, int vec, unsigned q[3][JIT_PX]) {
+  for (int c = 0; c < 3; ++c) {
+    if (vec) {
+      const unsigned w = *reinterpret_cast<const unsigned*>(img + c * hw + at);
+      for (int k = 0; k < JIT_PX; ++k) q[c][k] = (w >> (8 * k)) & 255u;
+    } else {
+      for (int k = 0; k < JIT_PX; ++k) q[c][k] = at + k < hw ? img[c * hw + at + k] : 0u;
+    }
+  }
+}
+
+// grid: (chunks of 256 * JIT_PX pixels, images); image i belongs to sample i % B.  sums[i] += the L of every pixel after the
+// operations in front of contrast.
+__global__ __launch_bounds__(256) void jitter_stats_kernel(const uint8_t* u8, int B, long hw, const uint8_t* apply, const float* alpha,
+                                                           const int* hue_shift, const uint8_t* order, int ops, unsigned* sums, int vec) {
+  const int img = blockIdx.y, b = img % B;
+  if (!apply[b]) return;                              // the whole block: no lane is left waiting in the reduction below
+  const jit_params P = jit_load(b, alpha, hue_shift, order, ops);
+  const long at = ((long)blockIdx.x * 256 + threadIdx.x) * JIT_PX;
+  int sum = 0;
+  if (at < hw) {
+    unsigned q[3][JIT_PX];
+    jit_fetch(u8 + (long)img * 3 * hw, hw, at, vec, q);
+    for (int k = 0; k < JIT_PX; ++k) {
+      if (at + k >= hw) break;
+      jit_rgb p{(int)q[0][k], (int)q[1][k], (int)q[2][k]};
+      jit_run(p, P, 0, -1);
+      sum += jit_luma(p);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);           // <= 64 * 4 * 255
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(sums + img, (unsigned)sum);
+}
+
+__global__ __launch_bounds__(256) void jitter_apply_kernel(const uint8_t* u8, int B, long hw, const uint8_t* apply, const float* alpha,
+                                                           const int* hue_shift, const uint8_t* order, int ops, const unsigned* sums,
+                                                           float* f32, int vec) {
+  const int img = blockIdx.y, b = img % B;
+  const long at = ((long)blockIdx.x * 256 + threadIdx.x) * JIT_PX;
+  if (at >= hw) return;
+  unsigned q[3][JIT_PX];
+  jit_fetch(u8 + (long)img * 3 * hw, hw, at, vec, q);
+  if (apply[b]) {
+    const jit_params P = jit_load(b, alpha, hue_shift, order, ops);
+    // ImageStat mean + 0.5, truncated:  (2 sum + n) / (2 n)  in integers
+    const int mean = (int)((2ull * sums[img] + (unsigned long long)hw) / (2ull * (unsigned long long)hw));
+    for (int k = 0; k < JIT_PX; ++k) {
+      if (at + k >= hw) break;
+      jit_rgb p{(int)q[0][k], (int)q[1][k], (int)q[2][k]};
+      const int stop = jit_run(p, P, 0, -1);
+      if (stop < 4) jit_run(p, P, stop, mean);
+      q[0][k] = (unsigned)p.r; q[1][k] = (unsigned)p.g; q[2][k] = (unsigned)p.b;
+    }
+  }
+  float* out = f32 + (long)img * 3 * hw + at;
+  for (int c = 0; c < 3; ++c) {
+    if (vec) {
+      *reinterpret_cast<float4*>(out + c * hw) =
+          make_float4(unit_from_u8(q[c][0]), unit_from_u8(q[c][1]), unit_from_u8(q[c][2]), unit_from_u8(q[c][3]));
+    } else {
+      for (int k = 0; k < JIT_PX && at + k < hw; ++k) out[c * hw + k] = unit_from_u8(q[c][k]);
+    }
+  }
+}
+
 inline int flat_blocks(long n) { long nb = (n + 255) / 256; return (int)(nb < 1 ? 1 : (nb > 8192 ? 8192 : nb)); }
 inline bool crop_shape_ok(int B, int H, int W, int ch, int cw) {
   return B > 0 && H > 0 && W > 0 && ch > 0 && cw > 0 && ch <= H && cw <= W && B <= 65535;
@@ -282,6 +452,23 @@ extern "C" int segsde_batchprep_plane(const uint8_t* src, int B, int H, int W, c
   if (!crop_shape_ok(B, H, W, ch, cw) || (!crop_xy && (ch != H || cw != W))) return SEGSDE_ERR_SHAPE;
   hipLaunchKernelGGL(plane_kernel, dim3(flat_blocks((long)B * ch * cw)), dim3(256), 0, ST(stream), src, B, H, W, crop_xy, flip, ch, cw,
                      out);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_batchprep_color_jitter(const uint8_t* u8, int images, int B, int h, int w, const uint8_t* apply,
+                                             const float* alpha, const int32_t* hue_shift, const uint8_t* order, int ops,
+                                             uint32_t* sums, float* f32_out, void* stream) {
+  if (!u8 || !apply || !alpha || !hue_shift || !order || !sums || !f32_out) return SEGSDE_ERR_NULL;
+  if (images <= 0 || images > 65535 || B <= 0 || images % B != 0 || h <= 0 || w <= 0 || ops < 0 || ops > 15) return SEGSDE_ERR_SHAPE;
+  const long hw = (long)h * w;
+  if (hw > SEGSDE_COLOR_JITTER_MAX_PIXELS) return SEGSDE_ERR_SHAPE;      // 255 * hw must fit the uint32 sum
+  const int vec = (hw & 3) == 0 && aligned16(f32_out, nullptr) && (reinterpret_cast<uintptr_t>(u8) & 3) == 0;
+  const dim3 grid(segsde_cdiv(hw, 256L * JIT_PX), images);
+  if (hipMemsetAsync(sums, 0, sizeof(uint32_t) * images, ST(stream)) != hipSuccess) return SEGSDE_ERR_NULL;
+  hipLaunchKernelGGL(jitter_stats_kernel, grid, dim3(256), 0, ST(stream), u8, B, hw, apply, alpha, hue_shift, order, ops, sums, vec);
+  SEGSDE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(jitter_apply_kernel, grid, dim3(256), 0, ST(stream), u8, B, hw, apply, alpha, hue_shift, order, ops, sums, f32_out, vec);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }

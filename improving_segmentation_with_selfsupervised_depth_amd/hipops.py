@@ -8,6 +8,7 @@ import ctypes
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1958,3 +1959,53 @@ def batchprep_plane(src, crop_xy, flip, ch, cw):
     check(_lib.lib().segsde_batchprep_plane(_p(src), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(out), _stream(src)),
           "batchprep_plane")
     return out
+
+
+COLOR_JITTER_MAX_PIXELS = (2 ** 32 - 1) // 255        # SEGSDE_COLOR_JITTER_MAX_PIXELS: 255 * h * w fits the uint32 sum of L
+
+
+def _host_table(t, B, cols, name):
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    if a.shape != ((B,) if cols is None else (B, cols)):
+        raise ValueError("%s must have shape %s, got %s" % (name, (B,) if cols is None else (B, cols), a.shape))
+    return a
+
+
+def batchprep_color_jitter(u8, apply, alpha, hue_shift, order, f32_out=None, ops=15):
+    """torchvision 0.7.0's PIL ColorJitter + ToTensor on planar uint8 images: u8 [...,B,3,h,w] (batchprep_crop's output; leading
+    dimensions are frames, whose images share the sample's parameters) -> float32 of the same shape.  Per-sample HOST tables
+    (numpy arrays or tensors; they are validated here and then uploaded): apply [B] bool, alpha [B,3] = the brightness, contrast
+    and saturation factors (cast to float32 as C casts a double), hue_shift [B] integers in 0..255 = (uint8)(hue_factor * 255),
+    order [B,4] = a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue per sample.  All four operations run in that
+    order.  ``ops``: bit i set = operation i runs (15, all four, is ColorJitter; alpha 1.0 is an exact identity of a blend, but a
+    hue step with shift 0 still alters pixels through its HSV round trip, so a single operation is run by masking the others)."""
+    u8 = _u8(u8, "u8")
+    if u8.dim() < 4 or u8.shape[-3] != 3:
+        raise ValueError("u8 must be [...,B,3,h,w], got %s" % (tuple(u8.shape),))
+    B, _, h, w = u8.shape[-4:]
+    if min(B, h, w) < 1:
+        raise ValueError("u8 is empty: %s" % (tuple(u8.shape),))
+    apply = _host_table(apply, B, None, "apply")
+    alpha = _host_table(alpha, B, 3, "alpha")
+    hue_shift = _host_table(hue_shift, B, None, "hue_shift")
+    order = _host_table(order, B, 4, "order")
+    if hue_shift.dtype.kind not in "iu":
+        raise ValueError("hue_shift must be integers")
+    if ((hue_shift < 0) | (hue_shift > 255)).any():
+        raise ValueError("hue_shift outside 0..255")
+    if order.dtype.kind not in "iu" or not (np.sort(order.astype(np.int64), axis=1) == np.arange(4)).all():
+        raise ValueError("every row of order must be a permutation of 0..3")
+    if h * w > COLOR_JITTER_MAX_PIXELS:
+        raise ValueError("images of %dx%d pixels: the contrast mean is summed in 32 bits, at most %d pixels" % (h, w, COLOR_JITTER_MAX_PIXELS))
+    if int(ops) != ops or not 0 <= ops <= 15:
+        raise ValueError("ops is a mask of the four operations (0..15)")
+    images = u8.numel() // (3 * h * w)
+    if images < 1 or images > 65535:
+        raise ValueError("%d images in one call (1..65535)" % images)
+    f32_out = _out_like(f32_out, tuple(u8.shape), torch.float32, u8, "f32_out")
+    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(u8.device, non_blocking=True)
+    tables = (dev(apply != 0, np.uint8), dev(alpha, np.float32), dev(hue_shift, np.int32), dev(order, np.uint8))
+    sums = torch.empty((images,), dtype=torch.int32, device=u8.device)
+    check(_lib.lib().segsde_batchprep_color_jitter(_p(u8), images, B, h, w, _p(tables[0]), _p(tables[1]), _p(tables[2]), _p(tables[3]),
+                                                   int(ops), _p(sums), _p(f32_out), _stream(u8)), "batchprep_color_jitter")
+    return f32_out

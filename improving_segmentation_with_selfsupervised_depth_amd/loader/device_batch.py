@@ -6,8 +6,13 @@ scales.  With ``DeviceBatchBuilder`` a DataLoader worker only decodes and hands 
 device (csrc/batchprep.hip) then produces exactly -- bit for bit -- what ``__getitem__`` plus collation produce.  This module is
 not part of the reference's import surface.
 
-Not covered: ``color_aug`` (torchvision's PIL ``ColorJitter``); ``("color_aug", f, 0)`` is ``("color", f, 0)``, as in the reference
-whenever colour augmentation is off (``cityscapes_joint.yml``).  There is no CPU path: without the HIP library every call raises.
+Colour augmentation (``augmentations.color_aug``, on in the ``cityscapes_monodepth_highres_dec*.yml`` configs) is covered with
+``color_aug=True``: per sample a coin, then torchvision's PIL ``ColorJitter`` (brightness, contrast, saturation, hue in a shuffled
+order, a uint8 image between every two) on the scale-0 image of every frame.  The arithmetic is that of the Pillow the fixtures
+were generated with (12.2.0: ``ImageEnhance``'s blend, ``convert("L")``, ``convert("HSV")`` and back), bit for bit.  torchvision
+itself is not installed where this was written: the draw order of ``ColorJitter.get_params`` and the PIL functional operations
+are restated from torchvision 0.7.0, the version the reference pins.  With ``color_aug=False`` (``cityscapes_joint.yml``)
+``("color_aug", f, 0)`` is ``("color", f, 0)``, the same tensor.  There is no CPU path: without the HIP library every call raises.
 """
 import math
 import random
@@ -68,6 +73,18 @@ def lanczos_half_table(h_out, w_out):
     return np.stack([lanczos_half_rows(h_out), lanczos_half_rows(w_out)])
 
 
+def _no_jitter(batch_size):
+    return {"apply": np.zeros((batch_size,), dtype=np.bool_), "factors": np.tile(np.array([1.0, 1.0, 1.0, 0.0]), (batch_size, 1)),
+            "order": np.tile(np.arange(4, dtype=np.uint8), (batch_size, 1))}
+
+
+def jitter_tables(factors):
+    """float64 [B,4] factors -> what the kernel reads: alpha float32 [B,3] (Pillow's blend takes a C float: the double is rounded
+    once) and hue_shift int32 [B] = ``np.uint8(hue_factor * 255)``, truncated toward zero and wrapped into 0..255"""
+    factors = np.asarray(factors, dtype=np.float64).reshape(-1, 4)
+    return factors[:, :3].astype(np.float32), (np.trunc(factors[:, 3] * 255.0).astype(np.int64) & 255).astype(np.int32)
+
+
 class DeviceBatchBuilder:
     """``builder(frames, lbl=..., ...)`` -> the dict a batch of ``SequenceSegmentationLoader.__getitem__`` collates to.
 
@@ -76,7 +93,8 @@ class DeviceBatchBuilder:
 
     def __init__(self, height, width, crop_h=None, crop_w=None, num_scales=4, frame_idxs=(0, -1, 1),
                  intrinsics=(2262.52, 2265.3017905988554, 1096.98, 513.137), full_res_shape=(2048, 1024), label_lut=None,
-                 n_classes=None, ignore_index=250, load_onehot=False, is_train=True, random_horizontal_flip=0.0):
+                 n_classes=None, ignore_index=250, load_onehot=False, is_train=True, random_horizontal_flip=0.0, color_aug=False,
+                 brightness=(0.8, 1.2), contrast=(0.8, 1.2), saturation=(0.8, 1.2), hue=(-0.1, 0.1)):
         self.height, self.width = int(height), int(width)
         self.is_train = bool(is_train)
         if crop_h is None or crop_w is None or not self.is_train:          # sequence_segmentation_loader.py:81-86
@@ -95,6 +113,8 @@ class DeviceBatchBuilder:
         if self.load_onehot and not n_classes:
             raise ValueError("load_onehot needs n_classes")
         self.random_horizontal_flip = float(random_horizontal_flip or 0.0)
+        self.color_aug = bool(color_aug)                                   # augmentations["color_aug"]; the ranges: :90-93
+        self.jitter_ranges = tuple((float(lo), float(hi)) for lo, hi in (brightness, contrast, saturation, hue))
         self.label_lut = None if label_lut is None else np.asarray(label_lut).astype(np.int64).reshape(256)
         self.level_sizes = [(self.crop_h, self.crop_w)]
         for _ in range(1, self.num_scales):
@@ -111,16 +131,33 @@ class DeviceBatchBuilder:
         (sequence_segmentation_loader.py:210-212, 259-260): the colour-augmentation coin (drawn whenever ``is_train``; its
         result is unused here), the flip coin if a flip is configured, ``randint`` for x1, then for y1.  With ``is_train=False``
         no coin is drawn and both ``randint`` calls are ``randint(0, 0)``, which still advance the generator as in the reference."""
+        if self.color_aug:
+            raise ValueError("a color_aug builder draws the jitter between the samples' crops: use draw_with_jitter()")
+        return self.draw_with_jitter(batch_size)[:2]
+
+    def draw_with_jitter(self, batch_size):
+        """``draw`` plus the colour jitter: (crops, flips, jitter).  Per sample the reference draws the coin, the flip coin if a
+        flip is configured, x1, y1 and then -- only when the builder has ``color_aug`` and the coin was > 0.5 (:210, :297-299) --
+        what torchvision 0.7.0's ``ColorJitter.get_params`` draws: ``random.uniform`` for brightness, contrast, saturation and hue
+        in that order, then one ``random.shuffle`` of the four operations.  ``jitter``: ``apply`` bool [B], ``factors`` float64
+        [B,4] (1, 1, 1, 0 where not applied) and ``order`` uint8 [B,4], the operation ids (0 brightness, 1 contrast, 2
+        saturation, 3 hue) in the order they run."""
         crops = np.zeros((batch_size, 2), dtype=np.int32)
         flips = np.zeros((batch_size,), dtype=np.bool_)
+        jitter = _no_jitter(batch_size)
         for b in range(batch_size):
-            if self.is_train:
-                random.random()
+            coin = random.random() if self.is_train else 0.0
             if self.is_train and self.random_horizontal_flip > 0.0:
                 flips[b] = random.random() < self.random_horizontal_flip
             crops[b, 0] = random.randint(0, self.width - self.crop_w)
             crops[b, 1] = random.randint(0, self.height - self.crop_h)
-        return crops, flips
+            if self.is_train and coin > 0.5 and self.color_aug:
+                jitter["apply"][b] = True
+                jitter["factors"][b] = [random.uniform(lo, hi) for lo, hi in self.jitter_ranges]
+                ops = [0, 1, 2, 3]
+                random.shuffle(ops)
+                jitter["order"][b] = ops
+        return crops, flips, jitter
 
     def get_K(self, u_offset, v_offset, do_flip):
         """the reference's get_K (:332-342), including its flip of v0"""
@@ -153,8 +190,9 @@ class DeviceBatchBuilder:
             self._dev[k] = make().to(device)
         return self._dev[k]
 
-    def colors(self, frames, crop_d, flip_d, inputs):
-        """the colour pyramid of every frame: one crop launch per frame, one launch per level for all frames together"""
+    def colors(self, frames, crop_d, flip_d, inputs, jitter=None):
+        """the colour pyramid of every frame: one crop launch per frame, one launch per level for all frames together; with a
+        ``jitter`` that applies to some sample, two more launches for the color_aug images of all frames"""
         first = frames[self.frame_idxs[0]]
         B, device = first.shape[0], first.device
         F = len(self.frame_idxs)
@@ -162,8 +200,12 @@ class DeviceBatchBuilder:
         color = torch.empty((F, B, 3, self.crop_h, self.crop_w), dtype=torch.float32, device=device)
         for i, f in enumerate(self.frame_idxs):
             H.batchprep_crop(frames[f], crop_d, flip_d, self.crop_h, self.crop_w, u8_out=u8[i], f32_out=color[i])
-            inputs[("color", f, 0)] = color[i]
-            inputs[("color_aug", f, 0)] = color[i]
+            inputs[("color", f, 0)] = inputs[("color_aug", f, 0)] = color[i]          # one tensor under both keys
+        if jitter is not None and jitter["apply"].any():
+            alpha, shift = jitter_tables(jitter["factors"])
+            aug = H.batchprep_color_jitter(u8, jitter["apply"], alpha, shift, jitter["order"])
+            for i, f in enumerate(self.frame_idxs):
+                inputs[("color_aug", f, 0)] = aug[i]
         for s in range(1, self.num_scales):
             table = self._cached(("lanczos", s), device, lambda: torch.from_numpy(self._tables[s]))
             u8, color = H.batchprep_pyramid_level(u8, table)
@@ -171,14 +213,24 @@ class DeviceBatchBuilder:
                 inputs[("color", f, s)] = color[i]
         return inputs
 
-    def __call__(self, frames, lbl=None, pseudo_depth=None, is_labeled=None, idx=None, crops=None, flips=None):
+    def __call__(self, frames, lbl=None, pseudo_depth=None, is_labeled=None, idx=None, crops=None, flips=None, jitter=None):
+        """``crops`` / ``flips`` / ``jitter``: what ``draw_with_jitter`` returns; drawn here when neither crops nor flips are given
+        (``jitter`` too on a ``color_aug`` builder, unless one is passed).  Crops or flips without a ``jitter`` augment nothing."""
         first = frames[self.frame_idxs[0]]
         B, device = first.shape[0], first.device
         for f in self.frame_idxs:
             if tuple(frames[f].shape) != (B, self.height, self.width, 3):
                 raise ValueError("frame %r: expected uint8 [%d,%d,%d,3], got %s" % (f, B, self.height, self.width, tuple(frames[f].shape)))
         if crops is None and flips is None:        # also on the validation path: the reference's random_crop draws randint(0, 0) there
-            crops, flips = self.draw(B)
+            crops, flips, drawn = self.draw_with_jitter(B)
+            jitter = drawn if jitter is None and self.color_aug else jitter
+        if jitter is not None:
+            if not self.color_aug:
+                raise ValueError("jitter passed to a builder without color_aug")
+            jitter = {"apply": np.asarray(jitter["apply"]).astype(np.bool_).reshape(B),
+                      "factors": np.asarray(jitter["factors"], dtype=np.float64).reshape(B, 4), "order": np.asarray(jitter["order"]).reshape(B, 4)}
+            if jitter["apply"].any() and not self.is_train:
+                raise ValueError("the validation path never augments (is_train=False)")
         crops = np.zeros((B, 2), np.int32) if crops is None else np.asarray(torch.as_tensor(crops).cpu(), dtype=np.int32).reshape(B, 2)
         flips = np.zeros((B,), np.bool_) if flips is None else np.asarray(torch.as_tensor(flips).cpu()).astype(np.bool_).reshape(B)
         if (crops < 0).any() or (crops[:, 0] > self.width - self.crop_w).any() or (crops[:, 1] > self.height - self.crop_h).any():
@@ -188,7 +240,7 @@ class DeviceBatchBuilder:
         flip_d = torch.from_numpy(flips.astype(np.uint8)).to(device, non_blocking=True) if flips.any() else None
 
         inputs = {}
-        self.colors(frames, crop_d, flip_d, inputs)
+        self.colors(frames, crop_d, flip_d, inputs, jitter)
 
         kk = torch.from_numpy(self.intrinsics(crops, flips)).to(device, non_blocking=True)     # one copy for all scales
         for s in range(self.num_scales):

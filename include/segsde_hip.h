@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 18
+#define SEGSDE_ABI_VERSION 19
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -616,6 +616,19 @@ int segsde_batchprep_labels(const uint8_t* lbl, int B, int H, int W, const int32
 /* one-channel 8-bit image (pseudo_depth, :272-273, :329-330): src [B,H,W] uint8 -> out [B,1,ch,cw] = u8 / 255 */
 int segsde_batchprep_plane(const uint8_t* src, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch, int cw,
                            float* out, void* stream);
+/* color_aug (:297-301, :318-322): torchvision 0.7.0's PIL ColorJitter + ToTensor on the planar level-0 crop that
+ * segsde_batchprep_crop writes.  u8 [images,3,h,w] -> f32_out [images,3,h,w]; image i belongs to sample i % B (images = F * B:
+ * the frames of a sample share its draw).  Per-sample DEVICE tables: apply uint8 [B] (0: f32_out = u8 / 255), alpha float32
+ * [B][3] = the brightness, contrast and saturation factors as C floats, hue_shift int32 [B] in 0..255 = (uint8)(hue_factor *
+ * 255), order uint8 [B][4] = the operation ids (0 brightness, 1 contrast, 2 saturation, 3 hue) in the order drawn; only the
+ * low two bits of an id are looked at, a row that is no permutation is the caller's to reject.  Pillow's 8-bit arithmetic:
+ * every operation reads and writes uint8, contrast blends with the mean L of the image as the operations before it left it
+ * (one mean per image).  ops: bit i set = operation i runs (15: all, as ColorJitter does; a cleared bit skips that operation
+ * in every sample).  sums: DEVICE uint32 [images] scratch for those means (zeroed here).  SEGSDE_ERR_SHAPE when h * w
+ * exceeds SEGSDE_COLOR_JITTER_MAX_PIXELS (the sum of L is kept in 32 bits), images is no multiple of B or ops is outside 0..15. */
+#define SEGSDE_COLOR_JITTER_MAX_PIXELS 16843009L /* (2^32 - 1) / 255 */
+int segsde_batchprep_color_jitter(const uint8_t* u8, int images, int B, int h, int w, const uint8_t* apply, const float* alpha,
+                                  const int32_t* hue_shift, const uint8_t* order, int ops, uint32_t* sums, float* f32_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,7 @@
 """Time the device batch builder (loader/device_batch.py) against the same work done by Pillow on one host core.
 
     python tools/device_batch.py [--batch 16] [--crop 512 1024] [--sources 512x1024 1024x2048] [--repeats 9] [--cpu-samples 7]
+    python tools/device_batch.py --color-aug [--batch 16] [--crop 512 1024]      # the colour-augmentation leg alone
 
 GPU: device events around (a) the kernels alone -- three crop launches, three pyramid launches, the label launch -- and (b) the
 whole ``builder(...)`` call, which adds the host's K / inv_K arithmetic and three small copies; warm-up, then the median and the
@@ -10,6 +11,10 @@ shapes (below) and divided by the kernel time.
 CPU: flip / crop / three chained LANCZOS resizes / ToTensor per frame, the label table as one full-image comparison per id, K / inv_K per scale -- the
 reference's __getitem__ without the decode, which both paths need -- on ONE thread; samples per second, and that times 16 as the
 (linear-scaling, so optimistic) rate of 16 loader workers.  Prints one JSON line.
+``--color-aug``: the whole ``builder(...)`` call on crop-sized frames without colour augmentation, with every sample augmented and
+with the jitter the builder draws itself (about half the samples); the two jitter launches alone (tables already on the device)
+against the bytes they must move -- the uint8 level-0 image read by both, the float32 image written once; and the four PIL
+operations of ColorJitter on the three frames of a sample on one host core.
 """
 import argparse
 import json
@@ -144,6 +149,90 @@ def cpu_side(args, H, W):
             "samples_per_s_one_core": 1.0 / med, "samples_per_s_16_cores_linear": 16.0 / med}
 
 
+def timed(fn, repeats, inner):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1) / inner)
+    return {"median": statistics.median(ms), "min": min(ms), "max": max(ms), "samples": len(ms)}
+
+
+def color_aug_gpu(args):
+    import random
+    from improving_segmentation_with_selfsupervised_depth_amd import _lib, hipops
+    from improving_segmentation_with_selfsupervised_depth_amd.loader.device_batch import jitter_tables
+    dev = torch.device("cuda")
+    B, (ch, cw) = args.batch, args.crop
+    g = torch.Generator(device="cpu").manual_seed(0)
+    frames = {f: torch.randint(0, 256, (B, ch, cw, 3), dtype=torch.uint8, generator=g).to(dev) for f in FRAMES}
+    plain = DeviceBatchBuilder(ch, cw)
+    aug = DeviceBatchBuilder(ch, cw, color_aug=True)
+    random.seed(0)
+    crops, flips, drawn = aug.draw_with_jitter(B)
+    rng = np.random.RandomState(0)
+    every = {"apply": np.ones(B, bool), "factors": np.column_stack([rng.uniform(0.8, 1.2, (B, 3)), rng.uniform(-0.1, 0.1, B)]),
+             "order": np.stack([rng.permutation(4) for _ in range(B)]).astype(np.uint8)}
+    out = {"samples_augmented_by_the_drawn_jitter": int(drawn["apply"].sum()),
+           "call_plain_ms": timed(lambda: plain(frames, crops=crops, flips=flips), args.repeats, args.inner),
+           "call_every_sample_ms": timed(lambda: aug(frames, crops=crops, flips=flips, jitter=every), args.repeats, args.inner),
+           "call_drawn_jitter_ms": timed(lambda: aug(frames, crops=crops, flips=flips, jitter=drawn), args.repeats, args.inner)}
+    # the two launches alone: level-0 uint8 image and tables already on the device
+    F = len(FRAMES)
+    u8 = torch.randint(0, 256, (F, B, 3, ch, cw), dtype=torch.uint8, generator=g).to(dev)
+    alpha, shift = jitter_tables(every["factors"])
+    tb = [torch.from_numpy(a).to(dev) for a in (every["apply"].astype(np.uint8), alpha, shift, every["order"])]
+    sums = torch.empty(F * B, dtype=torch.int32, device=dev)
+    f32 = torch.empty((F, B, 3, ch, cw), dtype=torch.float32, device=dev)
+    lib, p = _lib.lib(), lambda t: t.data_ptr()
+    stream = hipops._stream(u8)
+
+    def launches():
+        _lib.check(lib.segsde_batchprep_color_jitter(p(u8), F * B, B, ch, cw, p(tb[0]), p(tb[1]), p(tb[2]), p(tb[3]), 15, p(sums), p(f32),
+                                                     stream), "color_jitter")
+    out["launches_ms"] = timed(launches, args.repeats, args.inner)
+    rd, wr = 2 * u8.numel(), 4 * f32.numel()
+    t = out["launches_ms"]["median"] * 1e-3
+    out.update(read_mb=rd / 1e6, write_mb=wr / 1e6, achieved_gbs=(rd + wr) / t / 1e9, frac_of_8tbs=(rd + wr) / t / HBM_PEAK)
+    return out
+
+
+def color_aug_cpu(args):
+    """torchvision 0.7.0's PIL ColorJitter (restated: torchvision is not a dependency) on the three level-0 frames of one sample"""
+    from PIL import Image, ImageEnhance
+    ch, cw = args.crop
+    rng = np.random.RandomState(0)
+    imgs = [Image.fromarray(rng.randint(0, 256, (ch, cw, 3), dtype=np.uint8)) for _ in FRAMES]
+
+    def hue(im, f):
+        h, s, v = im.convert("HSV").split()
+        h = Image.fromarray(((np.asarray(h).astype(np.int64) + (int(f * 255) & 255)) & 255).astype(np.uint8))
+        return Image.merge("HSV", (h, s, v)).convert("RGB")
+    ops = [lambda im: ImageEnhance.Brightness(im).enhance(1.13), lambda im: ImageEnhance.Contrast(im).enhance(0.91),
+           lambda im: ImageEnhance.Color(im).enhance(1.07), lambda im: hue(im, -0.06)]
+
+    def sample(i):
+        for im in imgs:
+            for k in np.random.RandomState(i).permutation(4):
+                im = ops[k](im)
+    sample(0)
+    dt = []
+    for i in range(args.cpu_samples):
+        t0 = time.perf_counter()
+        sample(i)
+        dt.append(time.perf_counter() - t0)
+    med = statistics.median(dt)
+    return {"ms_per_sample": {"median": med * 1e3, "min": min(dt) * 1e3, "max": max(dt) * 1e3, "samples": len(dt)},
+            "samples_per_s_one_core": 1.0 / med}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -153,9 +242,16 @@ def main():
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--cpu-samples", type=int, default=7)
     ap.add_argument("--skip-gpu", action="store_true", help="CPU side only (no rate of the builder is reported)")
+    ap.add_argument("--color-aug", action="store_true", help="the colour-augmentation leg instead of the pyramid / label stage")
     args = ap.parse_args()
     if not args.skip_gpu and not torch.cuda.is_available():
         sys.exit("tools/device_batch.py measures on the GPU: no device visible")
+    if args.color_aug:
+        res = {"batch": args.batch, "crop": args.crop, "frames": len(FRAMES), "color_aug": {"cpu": color_aug_cpu(args)}}
+        if not args.skip_gpu:
+            res["color_aug"]["gpu"] = color_aug_gpu(args)
+        print(json.dumps(res))
+        return
     res = {"batch": args.batch, "crop": args.crop, "frames": len(FRAMES), "scales": 4, "sources": {}}
     for src in args.sources:
         H, W = (int(v) for v in src.split("x"))
