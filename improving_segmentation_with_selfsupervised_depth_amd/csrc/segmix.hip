@@ -9,6 +9,11 @@ namespace {
 inline int flat_blocks(long n) { long nb = (n + 255) / 256; return (int)(nb < 1 ? 1 : (nb > 4096 ? 4096 : nb)); }
 inline int ce_blocks(long n) { long nb = (n + 255) / 256; return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb)); }
 
+// Per-pixel loss of both forward kernels.  x[t] - mx is exact or rounded at the size of the difference, as in the reference's
+// log_softmax; (mx + logf(se)) - x[t] would round at the magnitude of mx and lose the shift invariance of the softmax (logits
+// offset by +300: 1e-5 per pixel instead of 1e-7).
+__device__ __forceinline__ float ce_nll(float xt, float mx, float se) { return logf(se) - (xt - mx); }
+
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, int ld, long M, int C, const int64_t* target,
                                                      int64_t ignore, const float* cw, const float* pw, double* part) {
   SEGSDE_SMEM;
@@ -22,7 +27,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, int ld
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
-    const float nll = (mx + logf(se)) - x[t];
+    const float nll = ce_nll(x[t], mx, se);
     float w = cw ? cw[t] : 1.f;
     den += (double)w;
     if (pw) w *= pw[m];
@@ -88,7 +93,7 @@ __global__ __launch_bounds__(256) void ce_fwd_dense_kernel(const float* logits, 
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
     float se = 0.f;
     for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
-    const float nll = (mx + logf(se)) - x[t];
+    const float nll = ce_nll(x[t], mx, se);
     float w = cw ? cw[t] : 1.f;
     den += (double)w;
     if (pw) w *= pw[m];
