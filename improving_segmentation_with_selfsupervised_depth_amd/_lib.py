@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -179,6 +179,10 @@ _SIGS = {
     "segsde_batchprep_labels": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, c_int64, c_int, P, P, P]),
     "segsde_batchprep_plane": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P]),
     "segsde_batchprep_color_jitter": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P]),
+    "segsde_batchprep_labels_rgb": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, c_int, P, c_int64, c_int, P, P, P]),
+    "segsde_batchprep_resample_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P]),
+    "segsde_batchprep_resample_cols": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P]),
+    "segsde_batchprep_resize_nearest": (c_int, [P, c_int, c_int, c_int, c_int, P]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -4,6 +4,8 @@
 //   crop_rgb_kernel   get_color's flip, random_crop's crop, ToTensor            (:145-150, :259-267, :319)
 //   pyramid_kernel    transforms.Resize(..., Image.ANTIALIAS) by exactly 2, chained level to level, + ToTensor  (:308-309, :319)
 //   labels_kernel     crop + flip + encode_segmap (a 256-entry table) + the one-hot planes              (:227-248, :324-327)
+//   labels_rgb_kernel the same for colour-coded label maps: Mapillary's encode_segmap, a colour table in LDS
+//                     (mapillary_vistas_loader.py:58-66)
 //   plane_kernel      crop + flip + ToTensor of the one-channel pseudo_depth image                      (:272-273, :329-330)
 //   jitter_*_kernel   the PIL ColorJitter of color_aug (brightness / contrast / saturation / hue in a drawn order) + ToTensor
 //                     (:297-301, :318-322); Pillow's 8-bit arithmetic restated, fp32 and fp64 exactly where Pillow uses them
@@ -218,6 +220,38 @@ __global__ __launch_bounds__(256) void labels_kernel(const uint8_t* lbl, int B, 
     const int64_t v = labeled ? lut[lbl[crop_src(b, y, x, H, W, crop_xy, flip, ch, cw)]] : ignore_index;
     out[e] = v;
     if (onehot) {                                     // ignore pixels and unlabeled samples: every plane zero
+      int64_t* oh = onehot + (long)b * n_classes * HW + p;
+      for (int c = 0; c < n_classes; ++c) oh[c * HW] = (labeled && v == c) ? 1 : 0;
+    }
+  }
+}
+// colour-coded label maps (mapillary_vistas_loader.py:58-66): the id of a pixel is the LAST colour of the table that equals its
+// RGB triple, 0 when none does; the id `ignore_id` (Mapillary's "unlabeled", 65) becomes ignore_index.  The table sits in LDS as
+// packed r | g << 8 | b << 16 words; every lane walks it in step, so the reads are broadcasts.
+__global__ __launch_bounds__(256) void labels_rgb_kernel(const uint8_t* lbl, int B, int H, int W, const int* crop_xy, const uint8_t* flip,
+                                                         int ch, int cw, const int* colors, int n_colors, int ignore_id,
+                                                         const uint8_t* is_labeled, int64_t ignore_index, int n_classes, int64_t* out,
+                                                         int64_t* onehot) {
+  SEGSDE_SMEM;
+  int* sc = reinterpret_cast<int*>(segsde_smem);
+  for (int i = threadIdx.x; i < n_colors; i += 256) sc[i] = colors[i] & 0xffffff;
+  __syncthreads();
+  const long HW = (long)ch * cw, total = (long)B * HW;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int b = (int)(e / HW);
+    const long p = e - b * HW;
+    const int y = (int)(p / cw), x = (int)(p - (long)y * cw);
+    const bool labeled = !is_labeled || is_labeled[b];
+    int64_t v = ignore_index;
+    if (labeled) {
+      const uint8_t* px = lbl + 3 * crop_src(b, y, x, H, W, crop_xy, flip, ch, cw);
+      const int rgb = (int)px[0] | ((int)px[1] << 8) | ((int)px[2] << 16);
+      int id = 0;
+      for (int l = 0; l < n_colors; ++l) id = sc[l] == rgb ? l : id;
+      v = id == ignore_id ? ignore_index : (int64_t)id;
+    }
+    out[e] = v;
+    if (onehot) {
       int64_t* oh = onehot + (long)b * n_classes * HW + p;
       for (int c = 0; c < n_classes; ++c) oh[c * HW] = (labeled && v == c) ? 1 : 0;
     }
@@ -442,6 +476,18 @@ extern "C" int segsde_batchprep_labels(const uint8_t* lbl, int B, int H, int W, 
   if (!crop_shape_ok(B, H, W, ch, cw) || (!crop_xy && (ch != H || cw != W)) || (onehot_out && n_classes <= 0)) return SEGSDE_ERR_SHAPE;
   hipLaunchKernelGGL(labels_kernel, dim3(flat_blocks((long)B * ch * cw)), dim3(256), 0, ST(stream), lbl, B, H, W, crop_xy, flip, ch, cw,
                      lut, is_labeled, ignore_index, n_classes, lbl_out, onehot_out);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_batchprep_labels_rgb(const uint8_t* lbl, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch,
+                                           int cw, const int32_t* colors, int n_colors, int ignore_id, const uint8_t* is_labeled,
+                                           int64_t ignore_index, int n_classes, int64_t* lbl_out, int64_t* onehot_out, void* stream) {
+  if (!lbl || !colors || !lbl_out) return SEGSDE_ERR_NULL;
+  if (!crop_shape_ok(B, H, W, ch, cw) || (!crop_xy && (ch != H || cw != W)) || (onehot_out && n_classes <= 0)) return SEGSDE_ERR_SHAPE;
+  if (n_colors <= 0 || n_colors > SEGSDE_LABEL_COLORS_MAX) return SEGSDE_ERR_SHAPE;
+  hipLaunchKernelGGL(labels_rgb_kernel, dim3(flat_blocks((long)B * ch * cw)), dim3(256), sizeof(int) * n_colors, ST(stream), lbl, B, H, W,
+                     crop_xy, flip, ch, cw, colors, n_colors, ignore_id, is_labeled, ignore_index, n_classes, lbl_out, onehot_out);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }

@@ -2009,3 +2009,55 @@ def batchprep_color_jitter(u8, apply, alpha, hue_shift, order, f32_out=None, ops
     check(_lib.lib().segsde_batchprep_color_jitter(_p(u8), images, B, h, w, _p(tables[0]), _p(tables[1]), _p(tables[2]), _p(tables[3]),
                                                    int(ops), _p(sums), _p(f32_out), _stream(u8)), "batchprep_color_jitter")
     return f32_out
+
+
+def batchprep_labels_rgb(lbl, crop_xy, flip, ch, cw, colors, ignore_id=-1, is_labeled=None, ignore_index=250, n_classes=0,
+                         want_onehot=False):
+    """lbl [B,H,W,3] uint8 colour-coded label map -> int64 [B,ch,cw]: the index of the last entry of `colors` (int32 [n], r | g << 8
+    | b << 16) equal to the pixel, 0 when none is; id `ignore_id` becomes ignore_index.  Optionally the one-hot planes."""
+    lbl = _u8(lbl, "lbl")
+    if lbl.dim() != 4 or lbl.shape[-1] != 3:
+        raise ValueError("lbl must be [B,H,W,3], got %s" % (tuple(lbl.shape),))
+    B, H, W, _ = lbl.shape
+    crop_xy, flip = _crop_args(B, crop_xy, flip)
+    if colors.dtype != torch.int32 or colors.dim() != 1:
+        raise TypeError("colors must be int32 [n]")
+    if is_labeled is not None and (is_labeled.dtype != torch.uint8 or tuple(is_labeled.shape) != (B,)):
+        raise TypeError("is_labeled must be uint8 [B]")
+    out = torch.empty((B, ch, cw), dtype=torch.int64, device=lbl.device)
+    onehot = torch.empty((B, n_classes, ch, cw), dtype=torch.int64, device=lbl.device) if want_onehot else None
+    check(_lib.lib().segsde_batchprep_labels_rgb(_p(lbl), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(colors.contiguous()),
+                                                 colors.numel(), int(ignore_id), _p(is_labeled), int(ignore_index), int(n_classes),
+                                                 _p(out), _p(onehot), _stream(lbl)), "batchprep_labels_rgb")
+    return out, onehot
+
+
+RESAMPLE_MAX_TAPS = 64        # SEGSDE_RESAMPLE_MAX_TAPS: the widest window table the resampling kernels stage
+
+
+def _resize_desc(desc):
+    if desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 8 or desc.shape[0] < 1 or not desc.is_contiguous():
+        raise TypeError("desc must be a contiguous int64 [n,8] tensor")
+    return desc
+
+
+def batchprep_resample_rows(desc, max_rows, Wd, max_taps, max_span):
+    """the horizontal pass of Pillow's 8-bit Lanczos resampler over the samples `desc` describes (int64 [n,8] on the device: src, dst,
+    bounds, weights, in_h, in_w, taps, 0; include/segsde_hip.h) -- loader/device_batch.pil_resize builds it"""
+    desc = _resize_desc(desc)
+    check(_lib.lib().segsde_batchprep_resample_rows(_p(desc), desc.shape[0], int(max_rows), int(Wd), int(max_taps), int(max_span),
+                                                    _stream(desc)), "batchprep_resample_rows")
+
+
+def batchprep_resample_cols(desc, row_bytes, Hd, max_taps, max_span):
+    """the vertical pass: rows of `row_bytes` bytes, Hd output rows per sample"""
+    desc = _resize_desc(desc)
+    check(_lib.lib().segsde_batchprep_resample_cols(_p(desc), desc.shape[0], int(row_bytes), int(Hd), int(max_taps), int(max_span),
+                                                    _stream(desc)), "batchprep_resample_cols")
+
+
+def batchprep_resize_nearest(desc, Hd, Wd, channels):
+    """Image.NEAREST through per-axis index tables (desc rows: src, dst, row table, column table, in_h, in_w, 0, 0)"""
+    desc = _resize_desc(desc)
+    check(_lib.lib().segsde_batchprep_resize_nearest(_p(desc), desc.shape[0], int(Hd), int(Wd), int(channels), _stream(desc)),
+          "batchprep_resize_nearest")

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 19
+#define SEGSDE_ABI_VERSION 20
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -629,6 +629,38 @@ int segsde_batchprep_plane(const uint8_t* src, int B, int H, int W, const int32_
 #define SEGSDE_COLOR_JITTER_MAX_PIXELS 16843009L /* (2^32 - 1) / 255 */
 int segsde_batchprep_color_jitter(const uint8_t* u8, int images, int B, int h, int w, const uint8_t* apply, const float* alpha,
                                   const int32_t* hue_shift, const uint8_t* order, int ops, uint32_t* sums, float* f32_out, void* stream);
+/* Colour-coded label maps (loader/mapillary_vistas_loader.py:58-66): lbl [B,H,W,3] uint8 -> lbl_out [B,ch,cw] int64 = the index
+ * of the LAST entry of colors (DEVICE int32 [n_colors], r | g << 8 | b << 16) that equals the pixel, 0 when none does; the id
+ * ignore_id (Mapillary's "unlabeled", 65; -1: none) becomes ignore_index.  Crop, flip, is_labeled and onehot_out as in
+ * segsde_batchprep_labels.  SEGSDE_ERR_SHAPE when n_colors is outside 1..SEGSDE_LABEL_COLORS_MAX. */
+#define SEGSDE_LABEL_COLORS_MAX 1024
+int segsde_batchprep_labels_rgb(const uint8_t* lbl, int B, int H, int W, const int32_t* crop_xy, const uint8_t* flip, int ch, int cw,
+                                const int32_t* colors, int n_colors, int ignore_id, const uint8_t* is_labeled, int64_t ignore_index,
+                                int n_classes, int64_t* lbl_out, int64_t* onehot_out, void* stream);
+
+/* pil_loader's resize (loader/loader_utils.py:23-43) in front of the stage above: decoded images of any size -> the working
+ * size (csrc/resize.hip).  Samples of one launch may differ in source size; each is described by one row of desc, DEVICE
+ * int64 [n][8] = { src, dst, bounds, weights (four DEVICE addresses), in_h, in_w, taps, 0 }.
+ *
+ * Image.ANTIALIAS (Pillow's 8-bit Lanczos resampler, Resample.c) on HWC RGB images is two passes with a uint8 image between
+ * them; a pass whose axis keeps its size is NOT launched (Pillow skips it).  Per axis and (in, out) pair the host supplies, by
+ * Pillow's float64 formula, bounds int32 [out][2] = (first source pixel, taps in use) and weights int32 [out][taps] =
+ * (int)(w * 2^22 +- 0.5); per output clip8((2^21 + sum_j weights[j] * pix[first + j]) >> 22).
+ *   resample_rows: src [in_h][in_w][3] -> dst [in_h][Wd][3] (the horizontal pass); max_rows >= every in_h.
+ *   resample_cols: src [in_h][row_bytes] -> dst [Hd][row_bytes] (the vertical pass; row_bytes = 3 * width; in_w is ignored).
+ * max_taps >= every row's taps; max_span >= the number of source pixels (rows) from the first window's start to the last
+ * window's end over any group of 64 outputs starting at a multiple of 64 (cols: 16 outputs at a multiple of 16).  Both size
+ * the LDS stage; bounds that do not fit it, or that leave the source, are pulled back inside, never followed.
+ * SEGSDE_ERR_UNSUPPORTED when max_taps exceeds SEGSDE_RESAMPLE_MAX_TAPS (a reduction by more than about 10.3) or the stage
+ * does not fit 64 KiB of LDS.
+ *
+ * Image.NEAREST on maps of 1 or 3 bytes per pixel: src [in_h][in_w][channels] -> dst [Hd][Wd][channels] =
+ * src[bounds[y]][weights[x]], the two being the source row of every output row (int32 [Hd]) and the source column of every
+ * output column (int32 [Wd]); indices outside the source are clamped. */
+#define SEGSDE_RESAMPLE_MAX_TAPS 64
+int segsde_batchprep_resample_rows(const void* desc, int n, int max_rows, int Wd, int max_taps, int max_span, void* stream);
+int segsde_batchprep_resample_cols(const void* desc, int n, int row_bytes, int Hd, int max_taps, int max_span, void* stream);
+int segsde_batchprep_resize_nearest(const void* desc, int n, int Hd, int Wd, int channels, void* stream);
 
 #ifdef __cplusplus
 }
