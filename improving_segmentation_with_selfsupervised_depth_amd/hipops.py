@@ -2061,3 +2061,131 @@ def batchprep_resize_nearest(desc, Hd, Wd, channels):
     desc = _resize_desc(desc)
     check(_lib.lib().segsde_batchprep_resize_nearest(_p(desc), desc.shape[0], int(Hd), int(Wd), int(channels), _stream(desc)),
           "batchprep_resize_nearest")
+
+
+# ----------------------------------------------------------------------------------------------
+# label selection (csrc/labelsel.hip; label_selection.py)
+# ----------------------------------------------------------------------------------------------
+DEPTH_ERROR_TYPES = ("abs", "abs_inv_log", "abs_inv", "sq", "abs_rel", "sq_rel", "abs_log")      # SEGSDE_DEPTH_ERR_*
+POOL_TRANSFORMS = ("none", "inv_clamp", "log_inv_clamp")                                          # SEGSDE_POOL_*
+LABELSEL_FPS_MAX_N = 32000                                                                        # SEGSDE_LABELSEL_FPS_MAX_N
+
+
+def _nchw_strides(x):
+    """element strides of a [B,C,H,W] view as the kernels read it (any layout: dense NCHW, channels-last, pitched slices)"""
+    return [int(s) for s in x.stride()]
+
+
+def labelsel_score(logits, disp_pred=None, disp_pseudo=None, error_types=(), want_maps=False, table=None):
+    """logits [B,C,H,W] (any strides), disp_pred / disp_pseudo [B,H,W]; error_types: names from DEPTH_ERROR_TYPES.
+    -> (table float32 [B, 1+T] = (entropy_mean, depth_error[0..T)), entropy_map [B,H,W] or None, error_maps [B,T,H,W] or None).
+    ``table``: an optional [B, 1+T] dense destination (rows of a larger score table).  Nothing is copied to the host."""
+    logits = _f32(logits, "logits")
+    B, C, Hh, W = logits.shape
+    T = len(error_types)
+    try:
+        codes = [DEPTH_ERROR_TYPES.index(t) for t in error_types]
+    except ValueError:
+        raise NotImplementedError(error_types)
+    if T:
+        disp_pred, disp_pseudo = _f32(disp_pred, "disp_pred").contiguous(), _f32(disp_pseudo, "disp_pseudo").contiguous()
+        if tuple(disp_pred.shape) != (B, Hh, W) or tuple(disp_pseudo.shape) != (B, Hh, W):
+            raise ValueError("disparities must be [B,H,W] = %s, got %s / %s" % ((B, Hh, W), tuple(disp_pred.shape),
+                                                                                tuple(disp_pseudo.shape)))
+    else:
+        disp_pred = disp_pseudo = None
+    if table is None:
+        table = torch.empty((B, 1 + T), dtype=torch.float32, device=logits.device)
+    elif tuple(table.shape) != (B, 1 + T) or not table.is_contiguous() or table.dtype != torch.float32:
+        raise ValueError("table must be a dense float32 [%d, %d]" % (B, 1 + T))
+    ent = torch.empty((B, Hh, W), dtype=torch.float32, device=logits.device) if want_maps else None
+    err = torch.empty((B, T, Hh, W), dtype=torch.float32, device=logits.device) if want_maps and T else None
+    L = _lib.lib()
+    nb = L.segsde_labelsel_score_workspace(B, Hh, W, T)
+    ws_ = _ws(nb, logits)
+    sb, sc, sh, sw = _nchw_strides(logits)
+    arr = (ctypes.c_int * max(T, 1))(*codes)
+    check(L.segsde_labelsel_score(_p(logits), sb, sc, sh, sw, B, C, Hh, W, _p(disp_pred), _p(disp_pseudo), arr, T, _p(table),
+                                  _p(ent), _p(err), _p(ws_), nb, _stream(logits)), "labelsel_score")
+    return table, ent, err
+
+
+def labelsel_pool(x, h, bank, row0, pool="avg", transform="none"):
+    """adaptive_{avg,max}_pool2d(x [B,C,H,W], (h, 2h)) -> rows [row0, row0+B) of the float32 bank [N, >= C*h*2h]"""
+    x = _f32(x, "features")
+    B, C, Hh, W = x.shape
+    if pool not in ("avg", "max"):
+        raise NotImplementedError(pool)
+    if bank.dtype != torch.float32 or bank.dim() != 2 or bank.stride(1) != 1:
+        raise ValueError("the bank is a float32 [N, D] tensor with dense rows")
+    sb, sc, sh, sw = _nchw_strides(x)
+    check(_lib.lib().segsde_labelsel_pool(_p(x), sb, sc, sh, sw, B, C, Hh, W, int(h), int(pool == "max"),
+                                          POOL_TRANSFORMS.index(transform), _p(bank), int(bank.stride(0)), int(bank.shape[0]),
+                                          int(row0), _stream(x)), "labelsel_pool")
+    return bank
+
+
+def labelsel_normalize_(bank, C, P):
+    """in place: (f - mean_c) / std_c per channel over the rows and the P positions of the bank [N, C*P] (torch.std_mean, unbiased)"""
+    if bank.dtype != torch.float32 or bank.dim() != 2 or bank.stride(1) != 1 or bank.shape[1] != C * P:
+        raise ValueError("the bank is a float32 [N, C*P] tensor with dense rows")
+    L = _lib.lib()
+    N = int(bank.shape[0])
+    nb = L.segsde_labelsel_normalize_workspace(N, int(C), int(P))
+    ws_ = _ws(nb, bank)
+    check(L.segsde_labelsel_normalize(_p(bank), int(bank.stride(0)), N, int(C), int(P), _p(ws_), nb, _stream(bank)),
+          "labelsel_normalize")
+    return bank
+
+
+def labelsel_distance(bank, p=2, bias=None, out=None):
+    """[N, D] bank -> [N, N] distances (p = 1 or 2, direct form), + bias[j] per column when given, zero diagonal.
+    ``out``: an optional float32 [N, >= N] destination with dense rows (its columns past N are left alone)."""
+    if bank.dtype != torch.float32 or bank.dim() != 2 or (bank.shape[1] > 1 and bank.stride(1) != 1):
+        raise ValueError("the bank is a float32 [N, D] tensor with dense rows")
+    N, D = int(bank.shape[0]), int(bank.shape[1])
+    if p not in (1, 2):
+        raise NotImplementedError("labelsel_distance: p = %r (only 1 and 2)" % (p,))
+    if out is None:
+        out = torch.empty((N, N), dtype=torch.float32, device=bank.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != N or out.shape[1] != N or (N > 1 and out.stride(1) != 1):
+        raise ValueError("out must be a float32 [N, N] view with dense rows")
+    if bias is not None:
+        bias = _f32(bias, "bias").to(bank.device).contiguous()
+        if bias.numel() != N:
+            raise ValueError("one bias per sample: got %d for %d" % (bias.numel(), N))
+    ld = int(bank.stride(0)) if N > 1 else D
+    ldo = int(out.stride(0)) if N > 1 else N
+    check(_lib.lib().segsde_labelsel_distance(_p(bank), ld, N, D, int(p), _p(bias), _p(out), ldo, _stream(bank)), "labelsel_distance")
+    return out
+
+
+def labelsel_farthest_point(dist, current, n_new, preselected=None):
+    """dist float32 [N, N] (dense rows); current: indices (list / tensor) of the current samples; preselected: indices or None.
+    -> (new indices, their distances) as two host lists of ints / a float32 CPU tensor: ONE device-to-host copy after the launch.
+    The selection on a matrix that holds NaN is unspecified."""
+    if dist.dtype != torch.float32 or dist.dim() != 2 or dist.shape[0] != dist.shape[1] or (dist.shape[1] > 1 and dist.stride(1) != 1):
+        raise ValueError("dist is a square float32 matrix with dense rows")
+    N = int(dist.shape[0])
+    cur = [int(c) for c in (current.tolist() if torch.is_tensor(current) else current)]
+    if not cur or min(cur) < 0 or max(cur) >= N:
+        raise ValueError("current samples must be a non-empty list of indices in [0, %d)" % N)
+    n_new = int(n_new)
+    cur_t = torch.tensor(cur, dtype=torch.int32).to(dist.device)
+    pre_t = None
+    if preselected is not None:
+        pre = [int(c) for c in (preselected.tolist() if torch.is_tensor(preselected) else preselected)]
+        if pre and (min(pre) < 0 or max(pre) >= N):
+            raise ValueError("preselected samples must be indices in [0, %d)" % N)
+        m = np.zeros(N, dtype=np.uint8)
+        m[pre] = 1
+        pre_t = torch.from_numpy(m).to(dist.device)
+    res = torch.zeros(1 + 2 * max(n_new, 1), dtype=torch.int32, device=dist.device)      # [count | indices | distances (fp32 bits)]
+    ld = int(dist.stride(0)) if N > 1 else N
+    check(_lib.lib().segsde_labelsel_farthest_point(_p(dist), ld, N, _p(cur_t), len(cur), _p(pre_t), n_new, _p(res[1:]),
+                                                    _p(res[1 + max(n_new, 1):]), _p(res), _stream(dist)), "labelsel_farthest_point")
+    host = res.cpu()
+    count = int(host[0])
+    idx = host[1:1 + count].tolist()
+    d = host[1 + max(n_new, 1):1 + max(n_new, 1) + count].view(torch.float32).clone()
+    return idx, d

@@ -57,6 +57,17 @@ def berhu(input, target, mask, apply_log=False):
     return torch.mean(torch.where(absdiff <= C, absdiff, (absdiff * absdiff + C * C) / (2 * C)))
 
 
+def pixel_wise_entropy(logits, normalize=False):
+    """reference loss.py:40-47: -sum_c p log2(p + 1e-30) / log2(C) of the class softmax -> [N,H,W], one pass of the score kernel
+    of csrc/labelsel.hip over the logits in whatever layout they have (forward only).  ``normalize``: (e - min) / (max - min)
+    over the whole tensor."""
+    assert logits.dim() == 4
+    ent = H.labelsel_score(logits.detach().float(), want_maps=True)[1]
+    if normalize:
+        ent = H.minmax_normalize(ent.reshape(1, -1)).reshape(ent.shape)
+    return ent
+
+
 def feature_distance(a, b):
     """``torch.dist(outputs["encoder_features"], outputs["imnet_features"], p=2)`` of the feature-distance term (train.py:480-483)
     on the HIP kernels: deterministic, the result a 0-dim tensor on the device"""

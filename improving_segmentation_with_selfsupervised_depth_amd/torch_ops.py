@@ -181,6 +181,29 @@ def feature_distance(a, b):
     return Fn.feature_distance(a, b)
 
 
+# ----------------------------------------------------------------------------------------------- label selection
+def _forward_only(name, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("segsde::%s is forward only: an input requires grad (detach it, or call under torch.no_grad())" % name)
+
+
+@_op("labelsel_distance(Tensor bank, int p=2, Tensor? bias=None) -> Tensor")
+def labelsel_distance(bank, p=2, bias=None):
+    """[N,D] feature bank -> [N,N] distances in the direct form (p = 1 or 2), + bias[j] on column j, zero diagonal: exact zeros for
+    identical rows, bitwise symmetric without bias (label_selection._calc_feature_distance; forward only)"""
+    _forward_only("labelsel_distance", bank, bias)
+    return H.labelsel_distance(bank, int(p), bias)
+
+
+@_op("labelsel_farthest_point(Tensor dist, Tensor current, int n_new, Tensor? preselected=None) -> (Tensor, Tensor)")
+def labelsel_farthest_point(dist, current, n_new, preselected=None):
+    """label_selection.iterative_farthest_point on matrix rows: -> (new row indices int64 [k], their distances float32 [k]), both
+    on the host, k <= n_new; NaN in the matrix: unspecified (forward only)"""
+    _forward_only("labelsel_farthest_point", dist)
+    idx, d = H.labelsel_farthest_point(dist, current, int(n_new), preselected)
+    return torch.tensor(idx, dtype=torch.int64), d
+
+
 def names():
     """qualified names of everything registered above"""
     return ["%s::%s" % (NAMESPACE, n) for n in SCHEMAS]

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 20
+#define SEGSDE_ABI_VERSION 21
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -661,6 +661,60 @@ int segsde_batchprep_labels_rgb(const uint8_t* lbl, int B, int H, int W, const i
 int segsde_batchprep_resample_rows(const void* desc, int n, int max_rows, int Wd, int max_taps, int max_span, void* stream);
 int segsde_batchprep_resample_cols(const void* desc, int n, int row_bytes, int Hd, int max_taps, int max_span, void* stream);
 int segsde_batchprep_resize_nearest(const void* desc, int n, int Hd, int Wd, int channels, void* stream);
+
+/* ---- label selection (label_selection.py of the reference: uncertainty scores, depth-feature diversity), csrc/labelsel.hip ----
+ * All sums are block partials in the workspace folded by a finish pass in a fixed order (no float atomics): every result is a
+ * pure function of the inputs.
+ *
+ * segsde_labelsel_score: the per-image scores of label_selection.py:449-488 in one pass.  logits [B,C,H,W] are read through
+ * their element strides (sb, sc, sh, sw: dense NCHW or channels-last); disp_pred / disp_pseudo are dense [B,H,W]; types is a HOST
+ * array of T (0..SEGSDE_LABELSEL_MAX_TYPES) SEGSDE_DEPTH_ERR_* codes.  table [B][1+T] (device) receives (mean entropy, mean error
+ * of every type); entropy_map [B,H,W] and error_maps [B,T,H,W] are optional (null = not wanted).  Entropy per pixel:
+ * -sum p log2(p + 1e-30) / log2(C), p = softmax with the maximum subtracted (loss/loss.py:40-47).  Every error map is multiplied
+ * by 1 - dilate(disp_pseudo < 0.07, 7, 3) (the maximum over the 7x7 window, zero padding) and rows >= (int)(0.87 * H) are zero;
+ * the means run over all H*W pixels.  2 <= C <= SEGSDE_LABELSEL_MAX_CLASSES, else SEGSDE_ERR_UNSUPPORTED (log2(1) = 0 divides).
+ * With T == 0 the two disparity pointers may be null. */
+enum { SEGSDE_DEPTH_ERR_ABS = 0, SEGSDE_DEPTH_ERR_ABS_INV_LOG = 1, SEGSDE_DEPTH_ERR_ABS_INV = 2, SEGSDE_DEPTH_ERR_SQ = 3,
+       SEGSDE_DEPTH_ERR_ABS_REL = 4, SEGSDE_DEPTH_ERR_SQ_REL = 5, SEGSDE_DEPTH_ERR_ABS_LOG = 6 };
+#define SEGSDE_LABELSEL_MAX_TYPES 7
+#define SEGSDE_LABELSEL_MAX_CLASSES 160
+size_t segsde_labelsel_score_workspace(int B, int H, int W, int T);
+int segsde_labelsel_score(const float* logits, long sb, long sc, long sh, long sw, int B, int C, int H, int W,
+                          const float* disp_pred, const float* disp_pseudo, const int* types, int T, float* table,
+                          float* entropy_map, float* error_maps, void* workspace, size_t workspace_bytes, void* stream);
+/* adaptive_avg_pool2d (is_max = 0) / adaptive_max_pool2d (is_max = 1) of x [B,C,H,W] (element strides) to (h, 2h) with PyTorch's
+ * bins  start = floor(i * H / oh), end = ceil((i + 1) * H / oh), written to rows [row0, row0 + B) of the float32 bank
+ * [N][ld_bank >= C*h*2h] in the element order of an NCHW flatten(1).  transform: SEGSDE_POOL_* applied to every input element
+ * first (label_selection.py:417-426: the depth / logdepth feature modes). */
+enum { SEGSDE_POOL_NONE = 0, SEGSDE_POOL_INV_CLAMP = 1 /* clamp(1/x, 0.1, 80) */, SEGSDE_POOL_LOG_INV_CLAMP = 2 /* its log */ };
+int segsde_labelsel_pool(const float* x, long sb, long sc, long sh, long sw, int B, int C, int H, int W, int h, int is_max,
+                         int transform, float* bank, long ld_bank, long N, long row0, void* stream);
+/* (f - mean_c) / std_c in place over the bank [N][ld >= C*P] (P = h*2h positions per channel), per channel over the N rows and
+ * P positions; std is the unbiased one of torch.std_mean (two passes: the mean, then the squared deviations from it, both
+ * accumulated in double).  A constant channel becomes 0/0 = NaN as in the reference. */
+size_t segsde_labelsel_normalize_workspace(long N, int C, int P);
+int segsde_labelsel_normalize(float* bank, long ld, long N, int C, int P, void* workspace, size_t workspace_bytes, void* stream);
+/* The N x N distance matrix of the bank rows (label_selection.py:574-624 without patch_wise): out[i][j] = (sum_k |a_ik - a_jk|^p)^(1/p),
+ * p = 2 or 1 (anything else: SEGSDE_ERR_UNSUPPORTED), in the direct form in fp32: the terms of each chunk of 32 features are summed
+ * in ascending k and the chunk sums join the total by a compensated (Kahan) addition, so the sources must not be built with
+ * fast-math (both build recipes use -ffp-contract=off and no -ffast-math).  Identical rows give exactly 0 and
+ * out[i][j] == out[j][i] bit for bit (only the tiles on and above the diagonal are computed; both halves are
+ * written).  Then, when bias (device [N], nullable) is given, out[i][j] += bias[j] (a column bias), and the diagonal is set to 0.
+ * out has leading dimension ldo >= N; columns >= N of a row are not touched. */
+int segsde_labelsel_distance(const float* bank, long ld, int N, int D, int p, const float* bias, float* out, long ldo,
+                             void* stream);
+/* iterative_farthest_point (label_selection.py:627-648) in one launch of one workgroup: the running minimum over the rows of
+ * the current samples and one membership byte per sample live in LDS (5 bytes per sample: N <= SEGSDE_LABELSEL_FPS_MAX_N, else
+ * SEGSDE_ERR_UNSUPPORTED).  dist: float32 [N][ld]; current: device int32 [n_current] (n_current >= 1, indices in [0, N));
+ * preselected: device uint8 [N] mask or null -- columns outside it read as 0 and stay in the competition.  Up to n_new times:
+ * the column with the largest running minimum wins (ties: the lowest index); if it is already a current sample the loop stops;
+ * otherwise it is recorded with its value, marked, and its row folded into the minimum.  out_idx int32 [n_new], out_dist
+ * float32 [n_new], out_count int32 [1] (device).  Comparisons only: bit-exact for a given matrix.  A matrix that holds NaN
+ * gives an unspecified selection. */
+#define SEGSDE_LABELSEL_FPS_MAX_N 32000
+int segsde_labelsel_farthest_point(const float* dist, long ld, int N, const int* current, int n_current,
+                                   const uint8_t* preselected, int n_new, int* out_idx, float* out_dist, int* out_count,
+                                   void* stream);
 
 #ifdef __cplusplus
 }
