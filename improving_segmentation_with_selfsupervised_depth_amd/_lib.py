@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -192,6 +192,10 @@ _SIGS = {
     "segsde_labelsel_normalize": (c_int, [P, c_long, c_long, c_int, c_int, P, c_size_t, P]),
     "segsde_labelsel_distance": (c_int, [P, c_long, c_int, c_int, c_int, P, P, c_long, P]),
     "segsde_labelsel_farthest_point": (c_int, [P, c_long, c_int, P, c_int, P, c_int, P, P, P, P]),
+    "segsde_render_labels": (c_int, [P, c_long, c_long, c_long, c_long, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
+    "segsde_render_unit_image": (c_int, [P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, P]),
+    "segsde_colorize_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "segsde_colorize": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P, P, c_size_t, P]),
 }
 EXPORTS = sorted(_SIGS)
 

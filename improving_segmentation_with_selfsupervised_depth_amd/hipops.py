@@ -2189,3 +2189,100 @@ def labelsel_farthest_point(dist, current, n_new, preselected=None):
     idx = host[1:1 + count].tolist()
     d = host[1 + max(n_new, 1):1 + max(n_new, 1) + count].view(torch.float32).clone()
     return idx, d
+
+
+# ----------------------------------------------------------------------------------------------
+# rendering of inference outputs (csrc/render.hip; inference.py is the caller)
+# ----------------------------------------------------------------------------------------------
+RENDER_UNMAPPED = ("keep", "zero")                # SEGSDE_RENDER_UNMAPPED_*
+RENDER_MAX_COLORS = 256                           # SEGSDE_RENDER_MAX_COLORS
+COLORIZE_MAX_N = 1024                             # SEGSDE_COLORIZE_MAX_N
+
+
+def _palette(label_colors, like):
+    """[n,3] colours (tensor, array, list of triples or the loaders' {id: colour} dict with ids 0..n-1) -> device uint8 [n,3]"""
+    if isinstance(label_colors, dict):
+        if sorted(label_colors) != list(range(len(label_colors))):
+            raise ValueError("a palette dict must have the keys 0..n-1")
+        label_colors = [label_colors[i] for i in range(len(label_colors))]
+    pal = label_colors if torch.is_tensor(label_colors) else torch.as_tensor(np.asarray(label_colors))
+    if pal.dim() != 2 or pal.shape[1] != 3 or pal.shape[0] < 1:
+        raise ValueError("the palette is [n,3], got %s" % (tuple(pal.shape),))
+    if pal.shape[0] > RENDER_MAX_COLORS:
+        raise NotImplementedError("palettes of more than %d colours" % RENDER_MAX_COLORS)
+    if pal.dtype != torch.uint8:
+        if pal.is_floating_point() or bool((pal < 0).any()) or bool((pal > 255).any()):
+            raise ValueError("palette entries are integers in 0..255")
+        pal = pal.to(torch.uint8)
+    return pal.to(like.device).contiguous()
+
+
+def render_labels(label_colors, logits=None, ids=None, unmapped="keep", return_ids=False):
+    """logits [B,C,H,W] (float32, any strides: dense NCHW, channels-last, slices) or ids [B,H,W] (int64 / uint8) -> uint8
+    [B,H,W,3] colours of the first-maximum class (and the uint8 id plane [B,H,W] with return_ids).  An id outside the palette
+    keeps its value as a grey (``keep``) or turns black (``zero``).  One launch."""
+    if (logits is None) == (ids is None):
+        raise ValueError("give either logits or ids")
+    if unmapped not in RENDER_UNMAPPED:
+        raise NotImplementedError("unmapped = %r (one of %s)" % (unmapped, RENDER_UNMAPPED))
+    src = logits if ids is None else ids
+    pal = _palette(label_colors, src)
+    if ids is None:
+        logits = _f32(logits, "logits")
+        if logits.dim() != 4:
+            raise ValueError("logits are [B,C,H,W], got %s" % (tuple(logits.shape),))
+        B, C, Hh, W = logits.shape
+        sb, sc, sh, sw = (int(s) for s in logits.stride())
+        code = 0
+    else:
+        if ids.dtype not in (torch.int64, torch.uint8):
+            raise TypeError("ids must be int64 or uint8, got %s" % ids.dtype)
+        if ids.dim() != 3:
+            raise ValueError("ids are [B,H,W], got %s" % (tuple(ids.shape),))
+        ids = ids.contiguous()
+        B, Hh, W = ids.shape
+        C, sb, sc, sh, sw = 0, 0, 0, 0, 0
+        code = 1 if ids.dtype == torch.int64 else 2          # SEGSDE_DTYPE_I64 / SEGSDE_DTYPE_U8
+    rgb = torch.empty((B, Hh, W, 3), dtype=torch.uint8, device=src.device)
+    out_ids = torch.empty((B, Hh, W), dtype=torch.uint8, device=src.device) if return_ids else None
+    nbytes = B * Hh * W * ((4 * C + 4) if ids is None else (ids.element_size() + 3))
+    _timed("hbm_render_labels", float(nbytes), src, lambda: check(_lib.lib().segsde_render_labels(
+        _p(logits), sb, sc, sh, sw, _p(ids), code, B, C, Hh, W, _p(pal), int(pal.shape[0]), RENDER_UNMAPPED.index(unmapped), _p(rgb),
+        _p(out_ids), _stream(src)), "render_labels"))
+    return (rgb, out_ids) if return_ids else rgb
+
+
+def render_unit_image(x):
+    """float32 image [B,C,H,W] in [0,1] (C = 1 or 3, any strides) -> uint8 [B,H,W,C]: mul(255), add(0.5), clamp(0,255), truncate"""
+    x = _f32(x, "image")
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError("the image is [B,1,H,W] or [B,3,H,W], got %s" % (tuple(x.shape),))
+    B, C, Hh, W = x.shape
+    sb, sc, sh, sw = (int(s) for s in x.stride())
+    out = torch.empty((B, Hh, W, C), dtype=torch.uint8, device=x.device)
+    _timed("hbm_render_unit_image", float(5 * B * C * Hh * W), x, lambda: check(_lib.lib().segsde_render_unit_image(
+        _p(x), sb, sc, sh, sw, B, C, Hh, W, _p(out), _stream(x)), "render_unit_image"))
+    return out
+
+
+def colorize(img, lut, mask_zero=False):
+    """img float32 [B,H,W]; lut float32 [N+3,3] (the map's N rows, then its under / over / bad colours) -> float32 [B,H,W,3]:
+    the reference's _colorize with max_percentile = 100, per image"""
+    img = _f32(img, "image").contiguous()
+    if img.dim() != 3:
+        raise ValueError("images are [B,H,W], got %s" % (tuple(img.shape),))
+    lut = _f32(lut, "lut")
+    if lut.dim() != 2 or lut.shape[1] != 3 or lut.shape[0] < 4:
+        raise ValueError("the table is [N+3,3], got %s" % (tuple(lut.shape),))
+    N = int(lut.shape[0]) - 3
+    if N > COLORIZE_MAX_N:
+        raise NotImplementedError("colour maps of more than %d entries" % COLORIZE_MAX_N)
+    lut = lut.to(img.device).contiguous()
+    B, Hh, W = img.shape
+    out = torch.empty((B, Hh, W, 3), dtype=torch.float32, device=img.device)
+    L = _lib.lib()
+    nb = L.segsde_colorize_workspace(B, Hh, W)
+    ws_ = _ws(nb, img)
+    _timed("hbm_colorize", float(20 * B * Hh * W), img, lambda: check(L.segsde_colorize(
+        _p(img), B, Hh, W, _p(lut), N, int(bool(mask_zero)), _p(out), _p(ws_), nb, _stream(img)), "colorize"))
+    return out

@@ -204,6 +204,32 @@ def labelsel_farthest_point(dist, current, n_new, preselected=None):
     return torch.tensor(idx, dtype=torch.int64), d
 
 
+# ----------------------------------------------------------------------------------------------- rendering of inference outputs
+@_op("render_labels(Tensor palette, Tensor? logits=None, Tensor? ids=None, str unmapped=\"keep\") -> (Tensor, Tensor)")
+def render_labels(palette, logits=None, ids=None, unmapped="keep"):
+    """logits [B,C,H,W] (first-maximum argmax) or ids [B,H,W] (int64 / uint8) -> (uint8 [B,H,W,3] colours of the uint8 [n,3]
+    palette, uint8 [B,H,W] ids); an id outside the palette stays a grey ("keep") or turns black ("zero")
+    (inference.render_segmentation; forward only)"""
+    _forward_only("render_labels", logits)
+    return H.render_labels(palette, logits=logits, ids=ids, unmapped=unmapped, return_ids=True)
+
+
+@_op("render_unit_image(Tensor x) -> Tensor")
+def render_unit_image(x):
+    """float32 [B,C,H,W], C = 1 or 3 -> uint8 [B,H,W,C] by save_image's mul(255).add_(0.5).clamp_(0, 255) and truncation
+    (forward only)"""
+    _forward_only("render_unit_image", x)
+    return H.render_unit_image(x.detach())
+
+
+@_op("colorize(Tensor img, Tensor lut, bool mask_zero=False) -> Tensor")
+def colorize(img, lut, mask_zero=False):
+    """the reference's _colorize at max_percentile = 100 per image: float32 [B,H,W] and the [N+3,3] table of a colour map (its N
+    rows, under, over, bad) -> float32 [B,H,W,3] (forward only)"""
+    _forward_only("colorize", img)
+    return H.colorize(img.detach(), lut, bool(mask_zero))
+
+
 def names():
     """qualified names of everything registered above"""
     return ["%s::%s" % (NAMESPACE, n) for n in SCHEMAS]

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 21
+#define SEGSDE_ABI_VERSION 22
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -715,6 +715,39 @@ int segsde_labelsel_distance(const float* bank, long ld, int N, int D, int p, co
 int segsde_labelsel_farthest_point(const float* dist, long ld, int N, const int* current, int n_current,
                                    const uint8_t* preselected, int n_new, int* out_idx, float* out_dist, int* out_count,
                                    void* stream);
+
+/* ---- rendering of inference outputs (inference.py:84-116, train.py:904-923 and _colorize, train.py:137-151, of the reference),
+ * csrc/render.hip.  The uint8 images are byte for byte what the reference hands to its file writer; the outputs are DENSE tensors
+ * whose base address is a multiple of 4 (else SEGSDE_ERR_UNSUPPORTED).  Integer work and comparisons only, except where stated.
+ *
+ * segsde_render_labels: class ids -> palette colours, rgb uint8 [B,H,W,3], and optionally the id plane ids_out uint8 [B,H,W]
+ * (ids above 255 saturate).  The ids are either the argmax over the C class planes of logits [B,C,H,W], read through their
+ * element strides (sb, sc, sh, sw: dense NCHW, channels-last, channel slices, pitched rows) -- first maximum, strict >, which is
+ * torch.max(1)[1] on the CPU for finite and infinite values; a pixel whose classes hold NaN is unspecified -- or, when logits is
+ * null, the map ids [B,H,W] (dense; ids_dtype SEGSDE_DTYPE_I64 or SEGSDE_DTYPE_U8; read as non-negative).  palette: device uint8
+ * [n][3], 1 <= n <= SEGSDE_RENDER_MAX_COLORS.  An id v >= n follows `unmapped`: KEEP writes min(v, 255) into the three channels
+ * (Cityscapes.decode_segmap_tocolor starts from a copy of the map and save_image clamps), ZERO writes black (the Mapillary and
+ * CamVid decoders start from zeros). */
+enum { SEGSDE_RENDER_UNMAPPED_KEEP = 0, SEGSDE_RENDER_UNMAPPED_ZERO = 1 };
+#define SEGSDE_RENDER_MAX_COLORS 256
+int segsde_render_labels(const float* logits, long sb, long sc, long sh, long sw, const void* ids, int ids_dtype, int B, int C,
+                         int H, int W, const uint8_t* palette, int n, int unmapped, uint8_t* rgb, uint8_t* ids_out, void* stream);
+/* float32 image x [B,C,H,W] (element strides; C = 1 or 3, else SEGSDE_ERR_UNSUPPORTED) -> out uint8 [B,H,W,C] as torchvision
+ * 0.7.0's save_image computes it: x.mul(255).add_(0.5).clamp_(0, 255), then truncation.  The product and the sum are two
+ * separately rounded fp32 operations (the sources must not be compiled with floating-point contraction); NaN gives 0, +-inf
+ * saturate. */
+int segsde_render_unit_image(const float* x, long sb, long sc, long sh, long sw, int B, int C, int H, int W, uint8_t* out,
+                             void* stream);
+/* _colorize(img, cmap, mask_zero, max_percentile = 100) per image of img [B,H,W] (dense float32) -> out float32 [B,H,W,3].
+ * Pass 1 leaves the block partials of np.min / np.max per image in the workspace; pass 2, in fp32 as numpy and matplotlib's
+ * Colormap.__call__ do it:  q = clip(x, vmin, vmax) / vmax,  s = q * N,  index = N-1 if s == N, else N (under) if s < 0, else
+ * N+1 (over) if s > N, else N+2 (bad) if s is NaN, else trunc(s);  out = lut[index], or (1,1,1) where mask_zero and x <= 0.
+ * lut: device float32 [N+3][3], rows 0..N-1 the map, then its under, over and bad colours; 1 <= N <= SEGSDE_COLORIZE_MAX_N.
+ * An all-zero image is 0/0 = NaN = the bad colour, as in the reference.  min / max / clip propagate NaN as numpy's do. */
+#define SEGSDE_COLORIZE_MAX_N 1024
+size_t segsde_colorize_workspace(int B, int H, int W);
+int segsde_colorize(const float* img, int B, int H, int W, const float* lut, int N, int mask_zero, float* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
