@@ -1,1 +1,1 @@
-from .metrics import runningScore  # noqa: F401
+from .metrics import runningDepthScore, runningScore  # noqa: F401

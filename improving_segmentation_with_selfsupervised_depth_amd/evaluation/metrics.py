@@ -69,3 +69,43 @@ class runningScore(object):
         self._host = np.zeros((self.n_classes, self.n_classes))
         if self._dev is not None:
             self._dev.zero_()
+
+
+DEPTH_METRIC_NAMES = H.DEPTH_ERROR_COLUMNS[:7]      # MonodepthLoss.depth_metric_names
+
+
+class runningDepthScore(object):
+    """Depth counterpart of ``runningScore``: the median-scaled monocular-depth errors, per image by one call of
+    ``hipops.depth_errors`` and averaged over the images that have a valid pixel (the evaluation protocol the metric names come
+    from).  ``update`` stays on the device and never synchronises; ``get_scores`` is one copy to the host."""
+
+    def __init__(self, min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, crop=None):
+        self.min_depth, self.max_depth = min_depth, max_depth
+        self.median_scaling, self.scale, self.crop = median_scaling, scale, crop
+        self._acc = None      # float64 [10]: the sums of the seven metrics and of the ratio, the images counted, the images skipped
+
+    def update(self, depth_gt, depth_pred):
+        """depth_gt, depth_pred: float32 [B,H,W] or [B,1,H,W] of one size"""
+        table = H.depth_errors(depth_gt.detach(), depth_pred.detach(), self.min_depth, self.max_depth, self.median_scaling,
+                               self.scale, self.crop)
+        has = table[:, 7:8] > 0                                            # n > 0; the other columns of a skipped image are NaN
+        vals = torch.cat([table[:, :7], table[:, 13:14]], 1)
+        vals = torch.where(has, vals, torch.zeros_like(vals))
+        hasf = has.to(torch.float64)
+        add = torch.cat([vals.sum(0), hasf.sum(0), (1.0 - hasf).sum(0)])
+        if self._acc is None:
+            self._acc = add
+        else:
+            assert self._acc.device == add.device, "runningDepthScore was updated from two devices"
+            self._acc += add
+
+    def get_scores(self):
+        """-> ({name: mean over images}, {"n_images", "n_skipped", "mean_ratio"}); NaN means when no image was counted"""
+        acc = np.zeros(10) if self._acc is None else self._acc.cpu().numpy()
+        n = acc[8]
+        mean = acc[:8] / n if n > 0 else np.full(8, np.nan)
+        return ({k: float(mean[i]) for i, k in enumerate(DEPTH_METRIC_NAMES)},
+                {"n_images": int(n), "n_skipped": int(acc[9]), "mean_ratio": float(mean[7])})
+
+    def reset(self):
+        self._acc = None

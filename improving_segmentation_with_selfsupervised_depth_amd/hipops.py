@@ -2286,3 +2286,48 @@ def colorize(img, lut, mask_zero=False):
     _timed("hbm_colorize", float(20 * B * Hh * W), img, lambda: check(L.segsde_colorize(
         _p(img), B, Hh, W, _p(lut), N, int(bool(mask_zero)), _p(out), _p(ws_), nb, _stream(img)), "colorize"))
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# depth evaluation (csrc/depthmetrics.hip; evaluation/metrics.py::runningDepthScore and MonodepthLoss.compute_depth_metrics call it)
+# ----------------------------------------------------------------------------------------------
+DEPTH_ERROR_COLUMNS = ("abs_rel", "sq_rel", "rms", "log_rms", "a1", "a2", "a3", "n", "n_a1", "n_a2", "n_a3", "med_gt", "med_pred",
+                       "ratio")                                             # SEGSDE_DEPTH_ERRORS_COLUMNS
+
+
+def _depth_map(t, name):
+    t = _f32(t, name)
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3:
+        raise ValueError("%s is [B,H,W] or [B,1,H,W], got %s" % (name, tuple(t.shape)))
+    return t.contiguous()
+
+
+def depth_errors(gt, pred, min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, crop=None):
+    """gt, pred float32 [B,H,W] or [B,1,H,W] (any strides) -> float64 [B,14] on the device, columns DEPTH_ERROR_COLUMNS: per image
+    the seven monocular-depth errors over the pixels with min_depth < gt < max_depth inside crop = (y0, y1, x0, x1), after scaling
+    pred by scale * median(gt) / median(pred) (exact medians, numpy's convention) and clamping it to [min_depth, max_depth]; then n,
+    the three threshold counts, the two medians and the ratio.  An image without a valid pixel: n = 0, NaN elsewhere.  No host
+    synchronisation."""
+    gt, pred = _depth_map(gt, "gt"), _depth_map(pred, "pred")
+    if gt.shape != pred.shape:
+        raise ValueError("gt %s and pred %s differ in shape" % (tuple(gt.shape), tuple(pred.shape)))
+    if gt.device != pred.device:
+        raise ValueError("gt is on %s, pred on %s" % (gt.device, pred.device))
+    B, Hh, W = (int(s) for s in gt.shape)
+    if B < 1 or Hh < 1 or W < 1:
+        raise ValueError("empty depth maps %s" % (tuple(gt.shape),))
+    y0, y1, x0, x1 = (0, Hh, 0, W) if crop is None else (int(c) for c in crop)
+    if not (0 <= y0 < y1 <= Hh and 0 <= x0 < x1 <= W):
+        raise ValueError("crop (y0, y1, x0, x1) = %r is empty or leaves the %d x %d image" % (crop, Hh, W))
+    if not 0 <= min_depth < max_depth:
+        raise ValueError("0 <= min_depth < max_depth expected, got %r, %r" % (min_depth, max_depth))
+    table = torch.empty((B, len(DEPTH_ERROR_COLUMNS)), dtype=torch.float64, device=gt.device)
+    L = _lib.lib()
+    nb = L.segsde_depth_errors_workspace(B, Hh, W)
+    ws_ = _ws(nb, gt)
+    _timed("hbm_depth_errors", float(8 * B * (y1 - y0) * (x1 - x0)), gt, lambda: check(L.segsde_depth_errors(
+        _p(gt), _p(pred), B, Hh, W, float(min_depth), float(max_depth), int(bool(median_scaling)), float(scale), y0, y1, x0, x1,
+        _p(table), _p(ws_), nb, _stream(gt)), "depth_errors"))
+    return table

@@ -349,6 +349,25 @@ class MonodepthLoss:
                     outputs[("color_identity", f, s)] = inputs[("color", f, 0)]
         self._cache = (cache, [outputs[("disp", s)] for s in self.scales])
 
+    def compute_depth_metrics(self, inputs, outputs, min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, crop=None):
+        """The errors ``depth_metric_names`` lists, of outputs[("depth", 0, 0)] (as generate_depth_test_pred / generate_images_pred
+        leave it) against inputs["depth_gt"] [B,1,Hg,Wg]: the prediction is resized to (Hg, Wg) bilinearly (align_corners=False)
+        when the sizes differ, scaled per image by median(gt) / median(pred) and clamped (hipops.depth_errors).
+        -> {name: 0-dim float64 device tensor}, the mean over the images of the batch that have a valid pixel (NaN when none
+        has); nothing is copied to the host."""
+        gt = inputs["depth_gt"]
+        pred = outputs[("depth", 0, 0)].detach()
+        if pred.dim() == 3:
+            pred = pred[:, None]
+        if tuple(pred.shape[-2:]) != tuple(gt.shape[-2:]):
+            # one channel: [B,1,H,W] and the kernel's [B,H,W,1] are the same memory
+            pred = H.resize_bilinear(pred.float().contiguous().permute(0, 2, 3, 1), tuple(gt.shape[-2:]), False).permute(0, 3, 1, 2)
+        table = H.depth_errors(gt.detach(), pred, min_depth, max_depth, median_scaling, scale, crop)
+        has = table[:, 7:8] > 0
+        vals = torch.where(has, table[:, :7], torch.zeros_like(table[:, :7]))
+        mean = vals.sum(0) / has.to(torch.float64).sum()
+        return {name: mean[i] for i, name in enumerate(self.depth_metric_names)}
+
     def compute_losses(self, inputs, outputs):
         """reference :118-192 -> {"loss/0".."loss/3", "loss"}"""
         disps = [outputs[("disp", s)] for s in self.scales]

@@ -230,6 +230,17 @@ def colorize(img, lut, mask_zero=False):
     return H.colorize(img.detach(), lut, bool(mask_zero))
 
 
+# ----------------------------------------------------------------------------------------------- depth evaluation
+@_op("depth_errors(Tensor gt, Tensor pred, float min_depth=0.001, float max_depth=80.0, bool median_scaling=True, float scale=1.0, "
+     "int[]? crop=None) -> Tensor")
+def depth_errors(gt, pred, min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, crop=None):
+    """per-image monocular-depth errors with exact median scaling: float32 [B,H,W] or [B,1,H,W] twice -> float64 [B,14], columns
+    hipops.DEPTH_ERROR_COLUMNS (forward only)"""
+    _forward_only("depth_errors", gt, pred)
+    return H.depth_errors(gt.detach(), pred.detach(), float(min_depth), float(max_depth), bool(median_scaling), float(scale),
+                          None if crop is None else tuple(int(c) for c in crop))
+
+
 def names():
     """qualified names of everything registered above"""
     return ["%s::%s" % (NAMESPACE, n) for n in SCHEMAS]

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 22
+#define SEGSDE_ABI_VERSION 23
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -748,6 +748,29 @@ int segsde_render_unit_image(const float* x, long sb, long sc, long sh, long sw,
 size_t segsde_colorize_workspace(int B, int H, int W);
 int segsde_colorize(const float* img, int B, int H, int W, const float* lut, int N, int mask_zero, float* out, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* ---- depth evaluation (the metrics of MonodepthLoss.depth_metric_names: abs_rel, sq_rel, rms, log_rms, a1, a2, a3 with median
+ * scaling, the usual monocular-depth protocol), csrc/depthmetrics.hip.  gt, pred: dense float32 [B,H,W] on the device; table:
+ * device float64 [B][SEGSDE_DEPTH_ERRORS_COLUMNS].  Comparisons and per-pixel arithmetic in fp32, sums in float64.  Per image:
+ *   valid pixel: gt > min_depth, gt < max_depth (a NaN gt is invalid), inside the crop [y0,y1) x [x0,x1) (full image: 0,H,0,W); n
+ *   of them.  med_gt, med_pred: the medians of gt and of pred over the valid pixels as np.median gives them for a float32 array
+ *   (odd n: the middle element; even n: (lo + hi) / 2 in fp32), bit for bit: an exact radix selection on the float bits in the
+ *   IEEE order of finite values (negative and subnormal predictions included).  A NaN prediction at a valid pixel, and which of
+ *   -0 / +0 a median is, are unspecified.
+ *   ratio = scale * (med_gt / med_pred) if median_scaling, else scale (one fp32 division, one fp32 multiplication).
+ *   p = min(max(pred * ratio, min_depth), max_depth), g = gt, t = max(g / p, p / g).
+ *   columns 0-6: abs_rel = mean |g - p| / g, sq_rel = mean (g - p)^2 / g, rms = sqrt(mean (g - p)^2), log_rms = sqrt(mean (log g -
+ *   log p)^2), a_k = #{t < 1.25^k} / n (k = 1, 2, 3); columns 7-13: n, n_a1, n_a2, n_a3, med_gt, med_pred, ratio.
+ *   An image without a valid pixel gets n = 0 and NaN in every other column.
+ * No host synchronisation, no copy to the host; launches and grid sizes depend on the arguments only.  Block partials are folded
+ * in a fixed order, counts are integer atomics: every result is a pure function of the inputs.
+ * SEGSDE_ERR_SHAPE: B, H, W <= 0, an empty crop or one outside the image, !(0 <= min_depth < max_depth).  SEGSDE_ERR_UNSUPPORTED:
+ * H * W >= 2^32, B > 65535, a workspace that is not 8-byte aligned.  The workspace size is that of the full image for any crop. */
+#define SEGSDE_DEPTH_ERRORS_COLUMNS 14
+size_t segsde_depth_errors_workspace(int B, int H, int W);
+int segsde_depth_errors(const float* gt, const float* pred, int B, int H, int W, float min_depth, float max_depth,
+                        int median_scaling, float scale, int y0, int y1, int x0, int x1, double* table, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
