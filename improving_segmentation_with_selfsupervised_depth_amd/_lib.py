@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -69,8 +69,6 @@ _SIGS = {
     "segsde_conv2d_winograd_fused2": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, P,
                                               c_int, P, P]),
     "segsde_conv2d_winograd_fused_dgrad": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P, c_int, c_int, P]),
-    "segsde_reflect_adjoint_borders": (c_int, [P, P, P, P, P, c_int, c_int, P]),
-    "segsde_reflect_adjoint_borders_ok": (c_int, [P, c_int]),
     "segsde_reflect_adjoint_borders2": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "segsde_conv2d_wgrad_winograd_fused_workspace": (c_size_t, [P]),
     "segsde_conv2d_wgrad_winograd_fused": (c_int, [P, P, P, P, c_int, P, P, c_size_t, P]),

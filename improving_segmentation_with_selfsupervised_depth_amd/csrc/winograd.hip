@@ -278,7 +278,8 @@ __global__ __launch_bounds__(256) void wino_weight_multi_kernel(const segsde_win
   const int lb = (int)blockIdx.x - jb.block0, tf = lb >= nblk ? 1 : 0;
   const long e = (long)(lb - tf * nblk) * 256 + threadIdx.x;
   if (e >= per) return;
-  // reserved & 1: the [16][K][N] layout of the one-kernel route (winograd_fused.hip): forward [16][I][O], data-gradient [16][O][I]
+  // reserved & 1: a pack of the one-kernel route (winograd_fused.hip): logical [16][K][N] -- forward [16][I][O], data-gradient
+  // [16][O][I] -- stored in that route's blocked layout (N % 64 == 0: the caller's duty, as for segsde_winograd_fused_pack)
   const int tr = tf ^ (jb.reserved & 1);
   const int A = tr ? jb.I : jb.O, Bn = tr ? jb.O : jb.I;
   const int b = (int)(e % Bn), a = (int)(e / Bn);
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(256) void wino_weight_multi_kernel(const segsde_win
   }
   const long plane = (long)A * Bn;
   float* base = tf ? jb.u_dgrad : jb.u_fwd;
-  const bool blocked = (jb.reserved & 2) && (Bn % 64 == 0);      // the one-kernel route's blocked layout (winograd_fused.hip)
+  const bool blocked = jb.reserved & 1;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float v0 = t[r][0], v1 = 0.5f * ((t[r][0] + t[r][1]) + t[r][2]), v2 = 0.5f * ((t[r][0] - t[r][1]) + t[r][2]), v3 = t[r][2];

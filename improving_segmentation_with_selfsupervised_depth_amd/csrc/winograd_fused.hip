@@ -14,13 +14,9 @@
 //    double-precision column sums of what it stored (the following BatchNorm's batch statistics, same partial-row format as
 //    the implicit-GEMM epilogue's).
 // 16 instead of 36 multiply-adds per output, and no transform traffic: x is read once (+ halo), y written once.
-#include <stdlib.h>
 #include <type_traits>
 #include "segsde_common.h"
 #include "winograd.h"
-#ifndef WINO_UP_SKIP
-#define WINO_UP_SKIP 1        // 0: build without the zero-position skipping of upsampled-source fills (A/B)
-#endif
 
 namespace {
 #define ST(s) static_cast<hipStream_t>(s)
@@ -43,11 +39,7 @@ constexpr int FCH = 64;                               // channels per LDS fill
 // 16 + 16 LDS instructions per thread instead of 64 + 64 (round 6: the epilogue was 5-14 % of the kernel, probe_r06_wino_phases.log)
 constexpr int FZP = 36;
 constexpr int F_FLOATS = 8 * 64 * FZP > FCH * FPS ? 8 * 64 * FZP : FCH * FPS;
-#ifdef WINO_DBG_OCC1           // phase-cost probe: one workgroup per CU (LDS request above half of the 160 KiB)
-constexpr size_t F_LDS = 96 * 1024;
-#else
 constexpr size_t F_LDS = (size_t)F_FLOATS * sizeof(float) + 2 * 4 * 64 * sizeof(double);
-#endif
 
 // the sources of the virtual input [up2x?(x0) | x1]: channels [0, C0) from x0 (stored at half resolution when up0: the decoder's
 // nearest upsampling, models/depth_decoder.py:91, is index arithmetic of the patch loader), [C0, C) from x1 at full resolution;
@@ -58,12 +50,11 @@ struct WinoSrc { const float* x0; const float* x1; int ld0, ld1, C0, up0; };
 // layer's input is the gradient of this ELU's output)
 struct WinoAg { const float* agy; int agld, agkind; };
 
-// UBLK: the transformed weights in the BLOCKED layout U[row w][c][block of 64 filters][32 lanes][4 positions of the row][2 filter
+// U: the transformed weights in the BLOCKED layout U[row w][c][block of 64 filters][32 lanes][4 positions of the row][2 filter
 // halves] -- the eight B operands of a lane and step are 32 contiguous bytes (two 16-byte requests, 1 KiB per wave-instruction)
-// instead of eight 4-byte requests in eight position planes
 // UPSKIP: the launch has a nearest-upsampled source (see the K loop).  A launch-level template parameter: as a run-time flag the
 // wave-uniform branches around the two MFMAs cost the single-source launches 2-4 % (probe_r06_upskip_single_source.log).
-template <bool STATS, bool UBLK, bool UPSKIP>
+template <bool STATS, bool UPSKIP>
 __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, int H, int W, int C, int reflect,
                                                             const float* U, int ldu, int Co, const float* bias, int act, float* y, int ldy,
                                                             double* part, int accumulate, WinoAg ag) {
@@ -127,10 +118,6 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
   };
 
   for (int c0 = 0; c0 < C; c0 += FCH) {
-#ifdef WINO_DBG_LOOP_ONLY      // phase-cost probe: the fill (loads, LDS writes, barriers) only once per workgroup
-    if (c0 == 0)
-#endif
-    {
     __syncthreads();                                   // the previous fill's reads are done
     {
       // all requests of the fill first (12 independent 16-byte loads per thread), then the transposing LDS writes
@@ -146,11 +133,6 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
       }
       const float* xs = sidx == 0 ? src.x0 : src.x1;
       const segsde_rsrc xr = segsde_make_rsrc(xs + (size_t)b * img + (sidx == 0 ? c0 : c0 - src.C0));
-#ifdef WINO_DBG_SKIP_LOAD      // phase-cost probe (tools/build_variant.sh): no global patch loads, the rest of the fill unchanged
-      (void)xr; (void)first;
-#pragma unroll
-      for (int i = 0; i < NL; ++i) { poff[i] = patch_offset(i); v[i] = make_float4((float)poff[i], 1.f, 2.f, 3.f); }
-#else
       if (first) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) { poff[i] = patch_offset(i); v[i] = segsde_buffer_load4(xr, poff[i], 0u); }
@@ -158,7 +140,6 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
 #pragma unroll
         for (int i = 0; i < NL; ++i) v[i] = segsde_buffer_load4(xr, poff[i], 0u);
       }
-#endif
 #pragma unroll
       for (int i = 0; i < NL; ++i) {
         const int e = tid + 256 * i;
@@ -170,7 +151,6 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
       }
     }
     __syncthreads();
-    }
     // U[p][c][n]: this lane's column n = co0 + nb * 32 + t of channel c0 + 2 s + kk, positions 4 wave + j.  The address is
     // split into a wave-uniform part (scalar registers, scalar adds) and the lane's constant 32-bit offset: the eight requests
     // of a step cost no vector instructions (with per-lane 64-bit pointers they were two thirds of the loop's VALU work, and
@@ -179,36 +159,22 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
     const segsde_rsrc ur = segsde_make_rsrc(U);
     // (ldu: row pitch of U -- Co, or the width of the pack this launch takes a column slice of)
     const unsigned nb64 = (unsigned)(ldu >> 6);
-    const unsigned lane_off = UBLK ? (unsigned)(kk * nb64 * 256 + t * 8) * 4u : (unsigned)(kk * ldu + t) * 4u;                          // bytes
-    const unsigned ubase = UBLK ? (unsigned)((((long)wave_u * C + c0) * nb64 + (co0 >> 6)) * 256 * 4)
-                                : (unsigned)((((long)(4 * wave_u) * C + c0) * ldu + co0) * 4);   // bytes; 16 C ldu floats < 2^30
-    const unsigned upos = (unsigned)((long)C * ldu * 4), ustep = UBLK ? 2u * nb64 * 256u * 4u : (unsigned)(2 * ldu * 4);
+    const unsigned lane_off = (unsigned)(kk * nb64 * 256 + t * 8) * 4u;                          // bytes
+    const unsigned ubase = (unsigned)((((long)wave_u * C + c0) * nb64 + (co0 >> 6)) * 256 * 4);   // bytes; 16 C ldu floats < 2^30
+    const unsigned ustep = 2u * nb64 * 256u * 4u;
     // B operands come straight from L2 (a few hundred ns): requested PD steps (PD x 512 MFMA cycles) ahead; the raw pixels
     // (LDS) one step ahead
     constexpr int PD = 4, NS = FCH / 2;
     float bv[PD][8], rv[2][8];
     auto fetch_b = [&](int s, int q) {
       const unsigned so = ubase + (unsigned)s * ustep;
-      if constexpr (UBLK) {
-        const float4 lo = segsde_buffer_load4(ur, lane_off, so), hi = segsde_buffer_load4(ur, lane_off, so + 16u);
-        bv[q][0] = lo.x; bv[q][1] = lo.y; bv[q][2] = lo.z; bv[q][3] = lo.w;
-        bv[q][4] = hi.x; bv[q][5] = hi.y; bv[q][6] = hi.z; bv[q][7] = hi.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          bv[q][2 * j] = segsde_buffer_load1(ur, lane_off, so + j * upos);
-          bv[q][2 * j + 1] = segsde_buffer_load1(ur, lane_off, so + j * upos + 128u);
-        }
-      }
+      const float4 lo = segsde_buffer_load4(ur, lane_off, so), hi = segsde_buffer_load4(ur, lane_off, so + 16u);
+      bv[q][0] = lo.x; bv[q][1] = lo.y; bv[q][2] = lo.z; bv[q][3] = lo.w;
+      bv[q][4] = hi.x; bv[q][5] = hi.y; bv[q][6] = hi.z; bv[q][7] = hi.w;
     };
     // (SEGSDE_LDS_READ_IMM: single ds_read_b32 with the plane / column offset in the instruction's 16-bit immediate off the two
     // row bases of the wave.  Left to itself the compiler pairs neighbouring columns into ds_read2_b32, whose 8-bit offsets do not
     // reach past the first plane: 124 v_add_u32 per fill to rebase them -- a third of the loop's vector instructions)
-#ifdef WINO_DBG_SKIP_K         // phase-cost probe: one step of the K loop instead of 32
-    constexpr int NS_RUN = 1;
-#else
-    constexpr int NS_RUN = NS;
-#endif
     // Software-pipelined step (round 6): the A operands of step s + 1 are formed during step s, and every request of a step sits
     // in the shadow of one of its MFMAs -- slots 0..3 issue the eight raw-pixel reads of the next step (two each), 4 / 5 the two
     // weight requests of step s + PD - 1, 6 / 7 the eight additions that turn the pixels into the next step's operands.  One wave
@@ -246,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
       form_a(0, 0); form_a(0, 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int s = 0; s < NS_RUN; ++s) {
+      for (int s = 0; s < NS; ++s) {
         const int q = s & 1, qb = s % PD;
         const bool nx = s + 1 < NS;
 #define WINO_MF_(j, nb, bi) acc[j][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(An[q][j], bv[qb][bi], acc[j][nb], 0, 0, 0); __builtin_amdgcn_sched_barrier(0)
@@ -268,19 +234,6 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
     }
   }
 
-#ifdef WINO_DBG_SKIP_EPI       // phase-cost probe: no Z exchange, no output
-  {
-    float sdbg = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sdbg += acc[j][nb][r];
-    if (sdbg == 1.2345678f) y[0] = sdbg;
-    return;
-  }
-#endif
   // ---- epilogue.  Y = A^T M A with A^T = [1 1 1 0; 0 1 -1 -1]: wave w holds row w of the 4 x 4 position grid, so the column
   // half (.) A runs on its accumulators (four values -> two); the rows meet in LDS as Z[w][column 0 / 1][tile][filter] (the
   // patch is dead by then), one round for all 64 filters, and every thread finishes eight tiles of one filter
@@ -401,9 +354,6 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] += oldv[q][k];
       }
-#ifdef WINO_DBG_FEW_STORES     // phase-cost probe: one tile of eight is stored
-      if (q == 0)
-#endif
       if (kBuf) {
         const unsigned s0 = (unsigned)((2 * ti) * W + 2 * tj) * (unsigned)ldy * 4u, sr = (unsigned)W * (unsigned)ldy * 4u, sc = (unsigned)ldy * 4u;
         if (accumulate & 2) {   // streaming stores (the launcher sets the bit for outputs that no cache level can hold)
@@ -435,13 +385,14 @@ __global__ __launch_bounds__(256, 2) void wino_fused_kernel(WinoSrc src, int B, 
   }
 }
 
-// OIHW 3x3 weight -> U (logical [16][K][N]; stored blocked -- wino_ublk_index -- or as sixteen [K][N] planes): forward (flip = 0) K = I, N = O; data-gradient (flip = 1: the convolution of dY with
-// the spatially flipped kernel) K = O, N = I.  thread (k, n), n fastest: coalesced writes, the nine reads of a thread are contiguous.
-// blocked layout (wino_fused_kernel<., true>): element (p = 4 r + q, k, n) at ((((r K + k) (N / 64) + n / 64) 32 + n % 32) 4 + q) 2 + (n / 32) % 2
+// OIHW 3x3 weight -> U (logical [16][K][N]; stored blocked -- wino_ublk_index; N a multiple of 64): forward (flip = 0) K = I, N = O;
+// data-gradient (flip = 1: the convolution of dY with the spatially flipped kernel) K = O, N = I.  thread (k, n), n fastest: the
+// nine reads of a thread are contiguous.
+// blocked layout (wino_fused_kernel): element (p = 4 r + q, k, n) at ((((r K + k) (N / 64) + n / 64) 32 + n % 32) 4 + q) 2 + (n / 32) % 2
 __device__ __forceinline__ long wino_ublk_index(int r, int q, int k, int n, int K, int N) {
   return (((((long)r * K + k) * (N >> 6) + (n >> 6)) * 32 + (n & 31)) * 4 + q) * 2 + ((n >> 5) & 1);
 }
-__global__ __launch_bounds__(256) void wino_weight_kn_kernel(const float* w, int O, int I, int flip, float* U, int blocked) {
+__global__ __launch_bounds__(256) void wino_weight_kn_kernel(const float* w, int O, int I, int flip, float* U) {
   const int K = flip ? O : I, N = flip ? I : O;
   const long e = blockIdx.x * 256L + threadIdx.x;
   if (e >= (long)K * N) return;
@@ -461,17 +412,11 @@ __global__ __launch_bounds__(256) void wino_weight_kn_kernel(const float* w, int
     tq[2][c] = 0.5f * ((k[0][c] - k[1][c]) + k[2][c]);
     tq[3][c] = k[2][c];
   }
-  const long plane = (long)K * N;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {          // (.) G^T
     const float v0 = tq[r][0], v1 = 0.5f * ((tq[r][0] + tq[r][1]) + tq[r][2]), v2 = 0.5f * ((tq[r][0] - tq[r][1]) + tq[r][2]), v3 = tq[r][2];
-    if (blocked) {
-      float* o = U + wino_ublk_index(r, 0, kq, nn, K, N);      // the four positions of a row: stride 2 floats
-      o[0] = v0; o[2] = v1; o[4] = v2; o[6] = v3;
-    } else {
-      float* out = U + e;
-      out[(4 * r + 0) * plane] = v0; out[(4 * r + 1) * plane] = v1; out[(4 * r + 2) * plane] = v2; out[(4 * r + 3) * plane] = v3;
-    }
+    float* out = U + wino_ublk_index(r, 0, kq, nn, K, N);      // the four positions of a row: stride 2 floats
+    out[0] = v0; out[2] = v1; out[4] = v2; out[6] = v3;
   }
 }
 
@@ -572,15 +517,6 @@ __global__ __launch_bounds__(256) void reflect_borders_kernel(BorderP p) {
   }
 }
 
-}  // namespace
-// layout of the one-kernel route's transformed weights: 1 = blocked (default), 0 = sixteen [K][N] planes (SEGSDE_WINO_FUSED_UBLK=0);
-// one answer per process -- the pack kernels (here and winograd.hip's multi-pack) and the convolution kernel must agree
-int segsde_wino_ublk() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("SEGSDE_WINO_FUSED_UBLK"); v = e ? (atoi(e) != 0) : 1; }
-  return v;
-}
-namespace {
 inline long fused_blocks(int B, int H, int W) {
   return (long)B * (((H >> 1) + FT_H - 1) / FT_H) * (((W >> 1) + FT_W - 1) / FT_W);
 }
@@ -598,9 +534,9 @@ extern "C" long segsde_winograd_fused_stats_rows(int B, int H, int W) { return f
 extern "C" int segsde_winograd_fused_pack(const float* w_oihw, int O, int I, int flip, float* U, void* stream) {
   if (!w_oihw || !U) return SEGSDE_ERR_NULL;
   if (O <= 0 || I <= 0) return SEGSDE_ERR_SHAPE;
+  if ((flip ? I : O) % 64 != 0) return SEGSDE_ERR_UNSUPPORTED;      // the blocked layout has no partial filter block
   const long total = (long)O * I;
-  const int blocked = segsde_wino_ublk() && ((flip ? I : O) % 64 == 0);
-  hipLaunchKernelGGL(wino_weight_kn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST(stream), w_oihw, O, I, flip, U, blocked);
+  hipLaunchKernelGGL(wino_weight_kn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST(stream), w_oihw, O, I, flip, U);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }
@@ -609,24 +545,18 @@ namespace {
 int launch_fused(const WinoSrc& src, int B, int H, int W, int C, int reflect, const float* u_kn, int ldu, int Cout, const float* bias, int act,
                  float* y, int ldy, int accumulate, double* stats, const WinoAg& ag, void* stream) {
   const dim3 grid((unsigned)fused_blocks(B, H, W), (unsigned)(Cout / 64));
-  const bool ublk = segsde_wino_ublk() != 0;
   // Outputs far beyond the 256 MiB of memory-side cache are written with streaming stores: nothing of them would be found in a cache by
   // their reader anyway, and they no longer push the patches' halo rows (re-read by the neighbouring workgroups) out of L2 / MALL
-  // (probe_r06_wino_nt.log: 128 -> 128 @128x256, a 268 MB output, -6 %; small maps unchanged).  SEGSDE_WINO_NT_MB: threshold, 0 = never.
-  static long nt_bytes = -1;
-  if (nt_bytes < 0) { const char* e = getenv("SEGSDE_WINO_NT_MB"); nt_bytes = (e ? atol(e) : 200L) << 20; }
-  accumulate = (accumulate ? 1 : 0) | ((nt_bytes > 0 && (long)B * H * W * Cout * 4 >= nt_bytes) ? 2 : 0);
+  // (probe_r06_wino_nt.log: 128 -> 128 @128x256, a 268 MB output, -6 %; small maps unchanged).
+  constexpr long nt_bytes = 200L << 20;
+  accumulate = (accumulate ? 1 : 0) | ((long)B * H * W * Cout * 4 >= nt_bytes ? 2 : 0);
   auto go = [&](auto k, double* st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS);
     hipLaunchKernelGGL(k, grid, dim3(256), F_LDS, ST(stream), src, B, H, W, C, reflect, u_kn, ldu, Cout, bias, act, y, ldy, st, accumulate, ag);
   };
-  static int upskip_on = -1;       // SEGSDE_WINO_UP_SKIP=0: never (A/B; hipops reads the same variable for its executed-flop count)
-  if (upskip_on < 0) { const char* e = getenv("SEGSDE_WINO_UP_SKIP"); upskip_on = e ? (atoi(e) != 0) : 1; }
-  const bool upskip = WINO_UP_SKIP && upskip_on && src.up0;
   auto pick = [&](auto st_tag, double* st) {
     constexpr bool ST = decltype(st_tag)::value;
-    if (upskip) { if (ublk) go(wino_fused_kernel<ST, true, true>, st); else go(wino_fused_kernel<ST, false, true>, st); }
-    else { if (ublk) go(wino_fused_kernel<ST, true, false>, st); else go(wino_fused_kernel<ST, false, false>, st); }
+    if (src.up0) go(wino_fused_kernel<ST, true>, st); else go(wino_fused_kernel<ST, false>, st);
   };
   if (stats) pick(std::true_type{}, stats); else pick(std::false_type{}, (double*)nullptr);
   SEGSDE_CHECK_LAUNCH();
@@ -665,7 +595,7 @@ extern "C" int segsde_conv2d_winograd_fused2(const float* x0, int ld0, int C0, i
 // saved activation output whose derivative multiplies the result (before the accumulation, like segsde_conv2d_dgrad_actgrad).
 // ldu: row pitch of ud_kn -- Cin, or, for the gradient of ONE source of a two-source convolution (the decoder's skip input,
 // channels [C0, C0 + C1) of the weight), the full pack's width with ud_kn pointing at the slice's first column.
-// A reflection-padded convolution's data-gradient is this call followed by segsde_reflect_adjoint_borders.
+// A reflection-padded convolution's data-gradient is this call followed by segsde_reflect_adjoint_borders2.
 extern "C" int segsde_conv2d_winograd_fused_dgrad(const float* dy, int lddy, int B, int H, int W, int Cout, const float* ud_kn, int ldu,
                                                   int Cin, float* dx, int lddx, int accumulate, const float* act_out, int act_ld,
                                                   int act_kind, void* stream) {

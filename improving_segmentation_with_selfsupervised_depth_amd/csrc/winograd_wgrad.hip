@@ -51,8 +51,8 @@ struct Geo {
 // whose 32 channels come from it skip the Winograd positions that are identically zero there (see `compute`).  Only these
 // launches carry the wave-uniform branches around the two MFMAs -- they cost a workgroup of the OTHER source 2-3 %
 // (probe_r06_upskip_wgrad.log), so launches where that source dominates keep the plain kernel.
-template <int WT_H, bool DB, int MINB, bool UPSKIP>
-__global__ __launch_bounds__(256, MINB) void wino_wgrad_fused_kernel(WgradP p) {
+template <int WT_H, bool DB, bool UPSKIP>
+__global__ __launch_bounds__(256, 2) void wino_wgrad_fused_kernel(WgradP p) {
   using G = Geo<WT_H>;
   SEGSDE_SMEM;
   float* lds = reinterpret_cast<float*>(segsde_smem);
@@ -280,9 +280,9 @@ int target_wgs() {
   return v;
 }
 // staging variant: 0 = 32-tile blocks, one stage; 1 = 16-tile blocks, two stages (the next block's loads fly during the
-// multiplies); 2 = 32-tile blocks, two stages, one workgroup per CU.  Measured (profiles/probe_r05_winograd_wgrad_*.log): 1 is
-// 2-3 % ahead on the large maps (>= 128 x 256 at batch 16: many blocks per workgroup), 0 on the small ones, 2 loses everywhere.
-// SEGSDE_WGRAD_FUSED_VAR forces one (read once per process).
+// multiplies).  Measured (profiles/probe_r05_winograd_wgrad_*.log): 1 is 2-3 % ahead on the large maps (>= 128 x 256 at batch 16:
+// many blocks per workgroup), 0 on the small ones.  SEGSDE_WGRAD_FUSED_VAR=0 / 1 forces one (read once per process; any other
+// value: not forced).
 int forced_variant() {
   static int v = -2;
   if (v == -2) { const char* e = getenv("SEGSDE_WGRAD_FUSED_VAR"); v = e ? atoi(e) : -1; }
@@ -290,7 +290,7 @@ int forced_variant() {
 }
 int variant(const segsde_conv_desc* d) {
   const int f = forced_variant();
-  if (f >= 0) return f;
+  if (f == 0 || f == 1) return f;
   return (long)d->B * d->H * d->W >= (1L << 19) ? 1 : 0;
 }
 int block_h(const segsde_conv_desc* d) { return variant(d) == 1 ? 2 : 4; }
@@ -347,25 +347,18 @@ extern "C" int segsde_conv2d_wgrad_winograd_fused(const segsde_conv_desc* d, con
   p.nbh = pl.nbh; p.nbw = pl.nbw; p.nblk = pl.nblk; p.S = pl.S; p.ncol = pl.ncol;
   p.part = static_cast<float*>(workspace);
   const dim3 grid((unsigned)(pl.ncol * pl.S));
-  const int var = variant(d);
   // zero-position skipping for upsampled-source channel blocks: only where that source carries at least half of the channels
-  // (SEGSDE_WINO_UP_SKIP=0: never)
-  static int upskip_on = -1;
-  if (upskip_on < 0) { const char* e = getenv("SEGSDE_WINO_UP_SKIP"); upskip_on = e ? (atoi(e) != 0) : 1; }
-  const bool upskip = upskip_on && p.up0 && 2 * d->C0 >= d->C0 + d->C1;
+  const bool upskip = p.up0 && 2 * d->C0 >= d->C0 + d->C1;
   auto go = [&](auto k, size_t lb) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
     hipLaunchKernelGGL(k, grid, dim3(256), lb, ST(stream), p);
   };
-  if (var == 1) {
+  if (variant(d) == 1) {
     const size_t lb = (size_t)2 * Geo<2>::STAGE * sizeof(float);
-    if (upskip) go(wino_wgrad_fused_kernel<2, true, 2, true>, lb); else go(wino_wgrad_fused_kernel<2, true, 2, false>, lb);
-  } else if (var == 2) {
-    const size_t lb = (size_t)2 * Geo<4>::STAGE * sizeof(float);
-    if (upskip) go(wino_wgrad_fused_kernel<4, true, 1, true>, lb); else go(wino_wgrad_fused_kernel<4, true, 1, false>, lb);
+    if (upskip) go(wino_wgrad_fused_kernel<2, true, true>, lb); else go(wino_wgrad_fused_kernel<2, true, false>, lb);
   } else {
     const size_t lb = (size_t)Geo<4>::STAGE * sizeof(float);
-    if (upskip) go(wino_wgrad_fused_kernel<4, false, 2, true>, lb); else go(wino_wgrad_fused_kernel<4, false, 2, false>, lb);
+    if (upskip) go(wino_wgrad_fused_kernel<4, false, true>, lb); else go(wino_wgrad_fused_kernel<4, false, false>, lb);
   }
   SEGSDE_CHECK_LAUNCH();
   return segsde_wino_wgrad_finish(p.part, pl.S, p.C, p.Co, dw_oihw, stream);

@@ -184,7 +184,8 @@ def winograd_packs_multi(weights, kn=False):
             else:
                 uf, ud = flat[off:off + n].view(16, O, I), flat[off + n:off + 2 * n].view(16, I, O)
             off += 2 * n
-            jobs[i] = _lib.WinoJob(w.data_ptr(), uf.data_ptr(), ud.data_ptr(), O, I, blk, (3 if WINO_FUSED_UBLK else 1) if kn else 0)
+            assert not kn or (O % 64 == 0 and I % 64 == 0), "the one-kernel route's pack layout has whole 64-filter blocks only"
+            jobs[i] = _lib.WinoJob(w.data_ptr(), uf.data_ptr(), ud.data_ptr(), O, I, blk, 1 if kn else 0)
             blk += 2 * ((O * I + 255) // 256)
             views.append((uf, ud))
         raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
@@ -194,7 +195,6 @@ def winograd_packs_multi(weights, kn=False):
     return views
 
 
-WINOGRAD_KEEP_V = os.environ.get("SEGSDE_WINOGRAD_KEEP_V", "1") != "0"   # a training forward keeps its transformed input for the weight gradient
 WINO_V = _Slot(None)     # the transformed input of the last _winograd(..., keep_v=True) call (ConvFn picks it up)
 
 
@@ -237,28 +237,18 @@ WINO_FUSED_MAX_CH = int(os.environ.get("SEGSDE_WINO_FUSED_MAX_CH", "256"))
 # round 5: the decoder's Conv3x3 on [upsample(x) | skip] (mirrored padding) through the same kernel -- upsampling and concat are
 # index arithmetic of its patch loader -- instead of the upsample-folded direct route, when the layer's folded multiply-add share
 # (4/9 on the upsampled channels, 9/9 on the skip) is above WINO_FUSED2_MIN_FOLD: the route runs all channels at 16/36 but at
-# ~0.75 of the direct kernel's multiply-add rate (profiles/probe_r05_*.log); SEGSDE_WINO_FUSED2=0: off
-WINO_FUSED2 = os.environ.get("SEGSDE_WINO_FUSED2", "1") != "0"
-# the kernels' zero-position skipping on nearest-upsampled sources (SEGSDE_WINO_UP_SKIP=0 switches it off in both csrc launchers;
-# here only the reported `executed` multiply-add counts depend on it)
-WINO_UP_SKIP = os.environ.get("SEGSDE_WINO_UP_SKIP", "1") != "0"
+# ~0.75 of the direct kernel's multiply-add rate (profiles/probe_r05_*.log)
 WINO_FUSED2_MAX_CIN = int(os.environ.get("SEGSDE_WINO_FUSED2_MAX_CIN", "768"))
 WINO_FUSED2_MIN_FOLD = float(os.environ.get("SEGSDE_WINO_FUSED2_MIN_FOLD", "0.6"))
 # round 5: data-gradients of the mirrored-padding Conv3x3 (zero-padded one-kernel launch + border launches) and data-gradients
-# with the activation-derivative epilogue on the one-kernel route; SEGSDE_WINO_FUSED_DGRAD_EXT=0 keeps them on the direct kernel
-WINO_FUSED_DGRAD_EXT = os.environ.get("SEGSDE_WINO_FUSED_DGRAD_EXT", "1") != "0"
+# with the activation-derivative epilogue on the one-kernel route.
 # the mirrored convolution's data-gradient takes the route from this many pixels on (measured, profiles/probe_r05_winograd_dgrad_*.log:
 # 1.35-1.6x from 16 x 64 x 128 pixels; at 16 x 32 x 64 the two border launches -- 64 workgroups with long reductions -- cost more
 # than the Winograd launch saves: 395 vs 338 us)
 WINO_FUSED_REFLECT_DGRAD_MIN_PIX = int(os.environ.get("SEGSDE_WINO_FUSED_REFLECT_DGRAD_MIN_PIX", str(1 << 17)))
 # the skip-source gradient of the decoder's two-source layers (dy -> the C1 encoder channels, mirrored padding, accumulated onto the
 # feature's gradient collector) on the one-kernel route -- a column slice of the flipped pack -- while the upsampled source's
-# low-resolution gradient stays on the folded route's 4x4 / stride-2 launch.  SEGSDE_WINO_FUSED_DGRAD2=0: off
-WINO_FUSED_DGRAD2 = os.environ.get("SEGSDE_WINO_FUSED_DGRAD2", "1") != "0"
-BORDERS2 = os.environ.get("SEGSDE_BORDERS2", "1") != "0"     # 0: the mirrored-padding terms as implicit-GEMM border launches (first version)
-# layout of the route's transformed weights: blocked (the eight B operands of a lane and step contiguous: two 16-byte requests
-# instead of eight 4-byte ones) unless SEGSDE_WINO_FUSED_UBLK=0 -- the library reads the same variable (segsde_wino_ublk)
-WINO_FUSED_UBLK = os.environ.get("SEGSDE_WINO_FUSED_UBLK", "1") != "0"
+# low-resolution gradient stays on the folded route's 4x4 / stride-2 launch.
 WINO_FUSED_TAKEN = {"fwd": 0, "dgrad": 0, "fwd2": 0, "dgrad_refl": 0, "dgrad_actgrad": 0, "dgrad2": 0, "wgrad": 0}
 
 
@@ -278,7 +268,7 @@ def _fused_shape_ok(B, H, W, cin, cout):
 def winograd_fused_ok(g, B=None, H=None, W=None, dgrad=False):
     """the shapes csrc/winograd_fused.hip takes: 3x3 / stride 1 / padding 1 / dilation 1, channel counts multiples of 64.
     One source at output resolution: up to WINO_FUSED_MAX_CH channels, zero or mirrored padding, forward and data-gradient
-    (mirrored: + segsde_reflect_adjoint_borders).  Forward on [upsample(x0) | x1] (g.up0): C0 % 64 == 0, up to
+    (mirrored: + segsde_reflect_adjoint_borders2).  Forward on [upsample(x0) | x1] (g.up0): C0 % 64 == 0, up to
     WINO_FUSED2_MAX_CIN input channels, when the folded route's multiply-add share is above WINO_FUSED2_MIN_FOLD."""
     if g.compute == 1:
         return False
@@ -288,11 +278,11 @@ def winograd_fused_ok(g, B=None, H=None, W=None, dgrad=False):
         return False
     if g.up0 or g.C1:
         # two sources without upsampling (the bottleneck-resolution layer) stay on the grouped route, which takes them
-        if dgrad or not (WINO_FUSED2 and g.up0 and g.C0 % 64 == 0 and cin <= WINO_FUSED2_MAX_CIN and cout <= WINO_FUSED_MAX_CH
+        if dgrad or not (g.up0 and g.C0 % 64 == 0 and cin <= WINO_FUSED2_MAX_CIN and cout <= WINO_FUSED_MAX_CH
                          and _fold_frac(g) >= WINO_FUSED2_MIN_FOLD):
             return False
     else:
-        if max(cin, cout) > WINO_FUSED_MAX_CH or (dgrad and g.reflect and not WINO_FUSED_DGRAD_EXT):
+        if max(cin, cout) > WINO_FUSED_MAX_CH:
             return False
     if B is None:
         return True
@@ -304,7 +294,7 @@ def winograd_fused_dgrad2_ok(g, B=None, H=None, W=None):
     convolution Cout -> C1 (+ border kernel)"""
     if g.compute == 1:
         return False
-    if not (WINOGRAD and WINO_FUSED and WINO_FUSED_DGRAD_EXT and WINO_FUSED_DGRAD2 and BORDERS2 and g.k == 3 and g.stride == 1 and g.dil == 1
+    if not (WINOGRAD and WINO_FUSED and g.k == 3 and g.stride == 1 and g.dil == 1
             and g.pad == 1 and g.reflect and g.up0 and g.C1 and g.cin_alg is None and g.C1 % 64 == 0 and g.Cout % 64 == 0
             and g.C0 % 64 == 0       # (the slice starts on a 64-filter block of the blocked pack layout)
             and g.Cout <= WINO_FUSED_MAX_CH and g.Cin <= WINO_FUSED2_MAX_CIN):
@@ -323,14 +313,13 @@ def winograd_fused_static_ok(conv):
     if max(conv.in_channels, conv.out_channels) <= WINO_FUSED_MAX_CH:
         return True
     # the decoder's two-source layers ([upsample(x) | skip], mirrored padding)
-    return bool(WINO_FUSED2 and getattr(conv, "reflect", False) and conv.out_channels <= WINO_FUSED_MAX_CH
-                and conv.in_channels <= WINO_FUSED2_MAX_CIN)
+    return bool(getattr(conv, "reflect", False) and conv.out_channels <= WINO_FUSED_MAX_CH and conv.in_channels <= WINO_FUSED2_MAX_CIN)
 
 
 class _KnPack(torch.Tensor):
-    """a transformed weight pack of the one-kernel route: 16 K N floats, logical shape [16][K][N], stored in the blocked order the
-    kernel reads (WINO_FUSED_UBLK; the sixteen [K][N] planes with SEGSDE_WINO_FUSED_UBLK=0) -- a plain tensor with a type the
-    dispatch can see; only the library's pack and convolution kernels interpret its contents"""
+    """a transformed weight pack of the one-kernel route: 16 K N floats, logical shape [16][K][N] (N % 64 == 0), stored in the blocked
+    order the kernel reads (include/segsde_hip.h, segsde_winograd_fused_pack) -- a plain tensor with a type the dispatch can see;
+    only the library's pack and convolution kernels interpret its contents"""
 
 
 def _kn(t):
@@ -352,8 +341,8 @@ def winograd_fused(kind, x, u_kn, bias=None, act="none", want_stats=False, tag=N
     """[up2x?(x) | x1] [B,H,W,C] NHWC -> act(conv3x3(.) + bias) [B,H,W,N] with u_kn [16][C][N]; (y, statistics partials or None).
     accumulate_into: a dense [B,H,W,N] tensor the result is added onto (and which is returned).
     Data-gradient extras: actgrad = (saved activation output [B,H,W,N], kind): the result is multiplied by the activation's
-    derivative; adjoint = (ConvGeom, wdpack): the convolution was mirror-padded -- the gradient of the padding cells is added by
-    segsde_reflect_adjoint_borders after the zero-padded launch."""
+    derivative; adjoint = the FORWARD pack [Cout][3][3][Cin]: the convolution was mirror-padded -- the gradient of the padding
+    cells is added by segsde_reflect_adjoint_borders2 after the zero-padded launch."""
     B, H0, W0, C0 = x.shape
     H, W = (2 * H0, 2 * W0) if up0 else (H0, W0)
     C1 = 0 if x1 is None else x1.shape[3]
@@ -380,7 +369,7 @@ def winograd_fused(kind, x, u_kn, bias=None, act="none", want_stats=False, tag=N
             _p(u_kn), N, _p(bias), ACT[act], _p(y), N, _p(part), _stream(x)), tagf,
             # issued multiply-adds: 16 / 36 of the algorithmic count, 9 / 36 on the channels of a nearest-upsampled source (seven of
             # the sixteen positions are identically zero there and skipped: csrc/winograd_fused.hip, UPSKIP)
-            executed=flops * ((9.0 * C0 + 16.0 * C1) / (36.0 * (C0 + C1)) if (up0 and WINO_UP_SKIP) else 16.0 / 36.0))
+            executed=flops * ((9.0 * C0 + 16.0 * C1) / (36.0 * (C0 + C1)) if up0 else 16.0 / 36.0))
         if rc == -4:
             return None
         check(rc, "conv2d_winograd_fused2")
@@ -391,24 +380,16 @@ def winograd_fused(kind, x, u_kn, bias=None, act="none", want_stats=False, tag=N
         ag_y, ag_kind = (actgrad[0], ACT[actgrad[1]]) if actgrad is not None else (None, 0)
         ag_ld = nhwc_ld(ag_y) if ag_y is not None else 0
         acc = 1 if accumulate_into is not None else 0
-        d = wdpack = wfpack = None
-        if adjoint is not None:
-            g, wdpack, wfpack = adjoint
-            if wfpack is None or not BORDERS2:
-                assert cols is None
-                d = _borders_desc(B, H, W, C, N, nhwc_ld(x))
+        wfpack = adjoint       # (the FORWARD pack of a mirrored convolution, or None)
 
         def launch():
-            # a column slice starts n_off floats into a row of the planar layout, n_off / 64 blocks of 256 floats into the blocked one
-            u_off = 4 * ((n_off // 64) * 256 if WINO_FUSED_UBLK else n_off)
+            u_off = 4 * (n_off // 64) * 256      # a column slice starts n_off / 64 blocks of 256 floats into the blocked layout
             rc = L.segsde_conv2d_winograd_fused_dgrad(_p(_f32(x)), nhwc_ld(x), B, H, W, C, ctypes.c_void_p(u_kn.data_ptr() + u_off), ldu,
                                                       N, _p(y), N, acc, _p(ag_y), ag_ld, ag_kind, _stream(x))
-            if rc == 0 and adjoint is not None:
-                if d is None:      # the border kernel of csrc/winograd_fused.hip (two launches), forward pack (its channel slice)
-                    rc = L.segsde_reflect_adjoint_borders2(_p(x), nhwc_ld(x), ctypes.c_void_p(wfpack.data_ptr() + 4 * n_off), wfpack.shape[3],
-                                                           _p(y), N, _p(ag_y), ag_ld, ag_kind, B, H, W, N, C, _stream(x))
-                else:              # four border launches of the implicit-GEMM kernel + corner kernel, data-gradient pack
-                    rc = L.segsde_reflect_adjoint_borders(ctypes.byref(d), _p(x), _p(wdpack), _p(y), _p(ag_y), ag_ld, ag_kind, _stream(x))
+            if rc == 0 and wfpack is not None:
+                # the border kernel of csrc/winograd_fused.hip (two launches), forward pack (its channel slice)
+                rc = L.segsde_reflect_adjoint_borders2(_p(x), nhwc_ld(x), ctypes.c_void_p(wfpack.data_ptr() + 4 * n_off), wfpack.shape[3],
+                                                       _p(y), N, _p(ag_y), ag_ld, ag_kind, B, H, W, N, C, _stream(x))
                 if rc == -4:
                     raise RuntimeError("the mirrored-padding launches declined a shape the one-kernel data-gradient took: "
                                        "the zero-padded part is already in dx (hipops.conv_dgrad must gate this)")
@@ -431,14 +412,12 @@ def winograd_fused(kind, x, u_kn, bias=None, act="none", want_stats=False, tag=N
     return y, part
 
 
-def _borders_desc(B, H, W, Cout, Cin, lddy):
-    return ConvDesc(B=B, H=H, W=W, C0=Cout, C1=0, ld0=lddy, ld1=0, up0=0, Ho=H, Wo=W, Cout=Cin, ldy=Cin, ldy2=0, nsplit=Cin, KH=3, KW=3,
-                    stride=1, dil=1, pad=1, pad_mode=PAD_REFLECT_ADJOINT, in_div=1, act=0, sum2x2=0, accumulate=1)
-
-
-def reflect_borders_ok(B, H, W, Cout, Cin, lddy, ag_ld=0):
-    """does segsde_reflect_adjoint_borders add the mirrored-padding gradient of this [B,H,W,Cout] -> [B,H,W,Cin] data-gradient"""
-    return bool(_lib.lib().segsde_reflect_adjoint_borders_ok(ctypes.byref(_borders_desc(B, H, W, Cout, Cin, lddy)), int(ag_ld)))
+def _reflect_borders2_ok(dy, H, W, Cin, Cout):
+    """the argument checks of segsde_reflect_adjoint_borders2 (csrc/winograd_fused.hip) on the gradient dy [B,H,W,Cout] -> dx
+    [B,H,W,Cin] that conv_dgrad is about to hand it (dx dense, the activation output checked by the caller): asked BEFORE the
+    zero-padded launch writes dx"""
+    return (H >= 4 and W >= 4 and Cin % 32 == 0 and Cout % 32 == 0 and Cout <= 1024 and nhwc_ld(dy) % 4 == 0
+            and dy.data_ptr() % 16 == 0)
 
 
 # round 5: the weight gradient on the one-kernel Winograd scheme (csrc/winograd_wgrad.hip): every 3x3 / stride-1 layer below 512
@@ -700,7 +679,7 @@ def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=Non
     elif wino is not None and not g.up0 and (not want_stats or (bias is None and act == "none")) and winograd_ok(g, B, H, W):
         WINO_V[0] = None
         r = _winograd("conv_fwd", g, x0, x1, wino, g.Cout, want_stats, flops, _tag(g, H, W), bias=bias, act=act, reflect=g.reflect,
-                      keep_v=keep_v and WINOGRAD_KEEP_V)
+                      keep_v=keep_v)
         if r is not None:
             return r if want_stats else r[0]
     if wfold is not None and not want_stats:
@@ -734,7 +713,8 @@ SKIP_ACCUMULATED = _Slot(False)   # did the last conv_dgrad(accumulate_skip_into
 def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_into=None, actgrad=None, fold=None, wino=None,
                accumulate_skip_into=None, wfpack=None):
     """Data gradient(s) of conv_forward w.r.t. (x0, x1).  dy: [B,Ho,Wo,Cout]; in_hw = (H, W) of the virtual input.
-    wfpack: the FORWARD pack, if the caller has it (the mirrored-padding border kernel of the one-kernel Winograd route reads it).
+    wfpack: the FORWARD pack, if the caller has it (the mirrored-padding border kernel of the one-kernel Winograd route reads it;
+    without it a mirrored convolution's data-gradient runs on the direct reflection-adjoint kernel).
     Returns (dx0, dx1); dx0 is at the *stored* resolution of x0 (2x2-summed when g.up0).
     accumulate_into: a dense [B,H,W,C0] tensor that already holds another gradient of x0 (single-source, non-upsampled
     convs): the result is ADDED to it in the kernel epilogue and that tensor is returned as dx0 (None is returned instead
@@ -756,14 +736,13 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         ag_ld = nhwc_ld(ag_y)
 
     if isinstance(wino, _KnPack):
-        ext = actgrad is not None or g.reflect
-        if (winograd_fused_ok(g, B, H, W, dgrad=True) and (Ho, Wo) == (H, W) and (not ext or WINO_FUSED_DGRAD_EXT)
-                and (not g.reflect or B * H * W >= WINO_FUSED_REFLECT_DGRAD_MIN_PIX)
-                and (not g.reflect or (wfpack is not None and BORDERS2 and H >= 4 and W >= 4 and g.C0 % 32 == 0 and Cout % 32 == 0 and Cout <= 1024)
-                     or reflect_borders_ok(B, H, W, Cout, g.C0, nhwc_ld(dy), ag_ld))
+        # (a mirrored convolution: the border kernel reads the FORWARD pack; without one the direct reflection-adjoint kernel below)
+        if (winograd_fused_ok(g, B, H, W, dgrad=True) and (Ho, Wo) == (H, W)
+                and (not g.reflect or (wfpack is not None and B * H * W >= WINO_FUSED_REFLECT_DGRAD_MIN_PIX
+                                       and _reflect_borders2_ok(dy, H, W, g.C0, Cout)))
                 and (actgrad is None or (ag_ld % 4 == 0 and ag_y.data_ptr() % 16 == 0))):
             r = winograd_fused("conv_dgrad", dy, wino, tag=_tag(g, H, W), accumulate_into=accumulate_into, actgrad=actgrad,
-                               adjoint=(g, wdpack, wfpack) if g.reflect else None)
+                               adjoint=wfpack if g.reflect else None)
             if r is not None:
                 ACTGRAD_FUSED[0] = actgrad is not None
                 return r[0], None
@@ -827,7 +806,7 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         if (dx1f is not None and isinstance(wino, _KnPack) and wfpack is not None and winograd_fused_dgrad2_ok(g, B, H, W)
                 and (Ho, Wo) == (H, W)):
             r = winograd_fused("conv_dgrad", dy, wino, tag="%d+0->%d k3 s1 d1 %dx%d refl skip-of-%d+%d" % (Cout, g.C1, H, W, g.C0, g.C1),
-                               accumulate_into=acc1, adjoint=(g, wdpack, wfpack), cols=(g.C0, g.C1))
+                               accumulate_into=acc1, adjoint=wfpack, cols=(g.C0, g.C1))
             if r is not None:
                 w1 = r[0]
                 WINO_FUSED_TAKEN["dgrad2"] += 1
@@ -916,7 +895,7 @@ def conv_wgrad(g, x0, x1, dy, wino_v=None, out=None):
                 # (9 / 36 on the upsampled source's channels where the launch skips its zero positions: that source carries at
                 # least half of the channels, csrc/winograd_wgrad.hip)
                 executed=flops * ((9.0 * g.C0 + 16.0 * g.C1) / (36.0 * g.Cin)
-                                  if (g.up0 and WINO_UP_SKIP and 2 * g.C0 >= g.Cin) else 16.0 / 36.0))
+                                  if (g.up0 and 2 * g.C0 >= g.Cin) else 16.0 / 36.0))
             if rc == 0:
                 WINO_FUSED_TAKEN["wgrad"] += 1
                 return dw

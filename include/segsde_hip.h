@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 23
+#define SEGSDE_ABI_VERSION 24
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -336,8 +336,8 @@ int segsde_nhwc_to_nchw(const float* x, int ldx, int B, int C, int H, int W, flo
  * otherwise (callers use segsde_conv2d_forward). */
 typedef struct segsde_wino_job {
   const float* w;    /* OIHW 3x3 weight */
-  float* u_fwd;      /* [16][O][I]  (reserved & 1: [16][I][O], the layout of segsde_conv2d_winograd_fused) */
-  float* u_dgrad;    /* [16][I][O]  (reserved & 1: [16][O][I]) */
+  float* u_fwd;      /* [16][O][I]  (reserved & 1: the pack of segsde_winograd_fused_pack, flip = 0; O % 64 == 0) */
+  float* u_dgrad;    /* [16][I][O]  (reserved & 1: the pack of segsde_winograd_fused_pack, flip = 1; I % 64 == 0) */
   int O, I, block0, reserved;
 } segsde_wino_job;
 size_t segsde_conv2d_winograd_workspace(const segsde_conv_desc* d);
@@ -359,10 +359,10 @@ int segsde_conv2d_wgrad_winograd(const segsde_conv_desc* d, const float* x0, con
  * (models/monodepth_layers.py:127-142, reflect = 1: mirrored padding, forward only) -- 3x3, stride 1, padding 1, one source, H and W
  * even, C % 64 == 0, Cout % 64 == 0.  segsde_winograd_fused_pack: OIHW -> the transformed weights U (16 K N floats) in the layout
  * the kernel reads -- blocked: [transform row][k][block of 64 n][32 lanes][4 positions of the row][2 halves of the block], the
- * eight B operands of a lane and step contiguous (round 5; SEGSDE_WINO_FUSED_UBLK=0 in the environment of the process selects
- * the sixteen [K][N] planes of round 4 for packs and kernel alike); flip = 0: the forward pack
+ * eight B operands of a lane and step contiguous; flip = 0: the forward pack
  * (K = Cin, N = Cout), flip = 1: the data-gradient pack of the spatially flipped kernel (K = Cout, N = Cin; call the convolution
- * with x = dY, C = Cout, Cout = Cin).  y = act(Y + bias) (bias nullable), or y += Y (accumulate = 1: no bias / activation /
+ * with x = dY, C = Cout, Cout = Cin).  The layout has no partial block: a pack whose N is not a multiple of 64 is
+ * SEGSDE_ERR_UNSUPPORTED (no kernel could read it).  y = act(Y + bias) (bias nullable), or y += Y (accumulate = 1: no bias / activation /
  * statistics; the gradient collector of DESIGN.md 3.2f); stats (nullable):
  * [segsde_winograd_fused_stats_rows(B, H, W)][2][Cout] doubles for segsde_bn_stats_from_partials.  SEGSDE_ERR_UNSUPPORTED outside
  * these shapes (segsde_winograd_fused_ok tells beforehand). */
@@ -380,25 +380,19 @@ int segsde_conv2d_winograd_fused2(const float* x0, int ld0, int C0, int up0, con
 /* Data-gradient on the one-kernel route with the direct route's epilogues: dx (+)= conv(dy, flipped pack) * act'(act_out)
  * (act_out nullable: the saved output of the activation that produced this convolution's input, ConvBlock's ELU,
  * monodepth_layers.py:108-125; accumulate: added onto what dx holds).  Zero padding; for the reflection-padded
- * Conv3x3 follow it with segsde_reflect_adjoint_borders (conv_igemm.hip): the gradient that entered the mirrored padding cells, as
- * four border launches + corner terms ADDED onto rows 1 / H-2 and columns 1 / W-2 of y (d = the descriptor of
- * segsde_conv2d_dgrad_actgrad with pad_mode = SEGSDE_PAD_REFLECT_ADJOINT; act_out as above).  ldu: row pitch of ud_kn (Cin; or,
+ * Conv3x3 follow it with segsde_reflect_adjoint_borders2: the gradient that entered the mirrored padding cells, ADDED onto rows
+ * 1 / H-2 and columns 1 / W-2 of dx (act_out as above).  ldu: row pitch of ud_kn (Cin; or,
  * for the gradient of ONE source of a two-source convolution -- the decoder's skip input, weight channels [C0, C0 + C1) -- the
  * full pack's width, ud_kn pointing at the slice's first 64-filter block (blocked layout: (first column / 64) * 256 floats into
  * the pack; the slice starts on a multiple of 64); segsde_reflect_adjoint_borders2 takes the matching slice of the forward pack
  * through ldw). */
 int segsde_conv2d_winograd_fused_dgrad(const float* dy, int lddy, int B, int H, int W, int Cout, const float* ud_kn, int ldu, int Cin,
                                        float* dx, int lddx, int accumulate, const float* act_out, int act_ld, int act_kind, void* stream);
-int segsde_reflect_adjoint_borders(const segsde_conv_desc* d, const float* dy, const float* wdpack, float* y, const float* act_out,
-                                   int act_ld, int act_kind, void* stream);
-/* The same mirrored-padding terms by a kernel of their own (csrc/winograd_fused.hip: two launches -- row lines, column lines +
- * corners -- of a 32-pixel x Cin MFMA kernel instead of five launches of the image-sized implicit-GEMM machinery); wpack = the
+/* The mirrored-padding terms by a kernel of their own (csrc/winograd_fused.hip: two launches -- row lines, column lines +
+ * corners -- of a 32-pixel x Cin MFMA kernel); wpack = the
  * FORWARD pack [Cout][3][3][Cin] of segsde_pack_weight(for_dgrad = 0).  Cin % 32 == 0, Cout % 32 == 0, H, W >= 4. */
 int segsde_reflect_adjoint_borders2(const float* dy, int lddy, const float* wpack, int ldw, float* dx, int lddx, const float* act_out,
                                     int act_ld, int act_kind, int B, int H, int W, int Cin, int Cout, void* stream);
-/* 1 when segsde_reflect_adjoint_borders takes the descriptor (act_ld: pixel pitch of act_out, 0 without one) -- asked before the
- * zero-padded launch writes dx */
-int segsde_reflect_adjoint_borders_ok(const segsde_conv_desc* d, int act_ld);
 /* Weight gradient on the one-kernel Winograd scheme (csrc/winograd_wgrad.hip): dU_p = V_p^T (A dY A^T)_p with both operands formed
  * from the raw input patches and the raw output gradient in LDS, split over tile ranges into slabs, folded deterministically and
  * transformed back (dW = G^T dU G, OIHW).  d as for segsde_conv2d_wgrad: 3x3 / stride 1 / padding 1 / dilation 1, zero or mirrored

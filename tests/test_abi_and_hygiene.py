@@ -69,6 +69,7 @@ def test_argument_validation_without_gpu():
     assert cdll.segsde_conv2d_winograd_fused(fake, 256, 1, 2048, 2048, 64, 0, fake, 64, None, 0, fake, 64, 0, None, None) == -4
     assert cdll.segsde_conv2d_winograd_fused_dgrad(fake, 256, 1, 2048, 2048, 64, fake, 64, 64, fake, 64, 0, None, 0, 0, None) == -4
     assert cdll.segsde_conv2d_winograd_fused2(fake, 64, 64, 0, fake, 256, 64, 1, 2048, 2048, 1, fake, 64, None, 0, fake, 64, None, None) == -4
+    assert cdll.segsde_winograd_fused_pack(fake, 64, 32, 1, fake, None) == -4             # N = 32: no partial block in the pack layout
     assert cdll.segsde_reflect_adjoint_borders2(None, 64, None, 64, None, 64, None, 0, 0, 2, 8, 16, 64, 64, None) == -1
     assert cdll.segsde_reflect_adjoint_borders2(fake, 64, fake, 64, fake, 64, None, 0, 0, 2, 3, 16, 64, 64, None) == -4         # H < 4
     assert cdll.segsde_dropout(None, 4, 10, 4, 0.5, 1, None, 4, None) == -1

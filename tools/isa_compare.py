@@ -9,13 +9,21 @@ The parent is the build before the decided experiment variants were removed (tem
 <.., MODEX>), the branch the one after (<.., MODE, CLAMP, CMP> and <.., MODE, CMP>): parent <128,128,2,2,4,32,16> pairs with branch
 <128,128,2,2,4,false,1>.  For every pair: LDS bytes equal, no scratch, VGPR / AGPR / SGPR counts not higher, occupancy not lower,
 instruction count not higher; and the basic blocks that hold v_mfma (the K loops) carry the same instruction sequence, operands
-included except the offsets of scalar loads from the kernel-argument segment.  Prints a markdown table; exit status 1 on a failure."""
+included except the offsets of scalar loads from the kernel-argument segment.  Prints a markdown table; exit status 1 on a failure.
+
+    tools/isa_compare.py --pairing wino parent/winograd_fused-...gfx950.s branch/winograd_fused-...gfx950.s  (+ winograd_wgrad, conv_igemm)
+
+pairs the kernels around the removal of the decided Winograd switches instead: parent wino_fused_kernel<STATS, true, UPSKIP> with branch
+<STATS, UPSKIP> (the planar weight layout, <., false, .>, has no successor), parent wino_wgrad_fused_kernel<H, DB, 2, UPSKIP> with
+branch <H, DB, UPSKIP> (staging variant 2, <4, true, 1, .>, has none), reflect_borders_kernel and every conv_igemm_kernel /
+conv_wgrad_kernel with the instantiation of the same arguments."""
 import re
 import sys
 
 INFO = {"lds": r"; LDSByteSize: (\d+)", "scratch": r"; ScratchSize: (\d+)", "vgpr": r"; NumVgprs: (\d+)", "agpr": r"; NumAgprs: (\d+)",
         "sgpr": r"; TotalNumSgprs: (\d+)", "occ": r"; Occupancy: (\d+)"}
 KERNELS = ("conv_igemm_kernel", "conv_wgrad_kernel", "colreduce_kernel")
+WINO_KERNELS = ("conv_igemm_kernel", "conv_wgrad_kernel", "wino_fused_kernel", "wino_wgrad_fused_kernel", "reflect_borders_kernel")
 
 
 def parse(path):
@@ -77,6 +85,16 @@ def parent_key(name):
     return branch_key(name)
 
 
+def parent_key_wino(name):
+    if "wino_fused_kernel" in name:
+        (stats, ublk, upskip), rest = targs(name, "wino_fused_kernel")
+        return ("wino_fused_kernel", (stats, upskip), rest) if ublk else None
+    if "wino_wgrad_fused_kernel" in name:
+        (wt_h, db, minb, upskip), rest = targs(name, "wino_wgrad_fused_kernel")
+        return ("wino_wgrad_fused_kernel", (wt_h, db, upskip), rest) if minb == 2 else None
+    return branch_key(name)
+
+
 def norm(ins):
     ins = re.sub(r"\.LBB\d+_\d+", ".LBB", ins)
     if ins.startswith("s_load_"):      # kernel-argument offsets moved: ConvP lost a field, the kernels lost an argument
@@ -89,6 +107,12 @@ def mfma_blocks(k):
 
 
 def main(argv):
+    global KERNELS, parent_key
+    if argv[:1] == ["--pairing"]:
+        assert argv[1] in ("tune", "wino"), argv[1]
+        if argv[1] == "wino":
+            KERNELS, parent_key = WINO_KERNELS, parent_key_wino
+        argv = argv[2:]
     pairs = list(zip(argv[0::2], argv[1::2]))
     rows, bad, dropped = [], [], []
     for ppath, bpath in pairs:

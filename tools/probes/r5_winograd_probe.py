@@ -2,7 +2,7 @@
 they replace -- (a) data-gradient of the mirrored Conv3x3 with the ELU derivative in the epilogue (direct reflection-adjoint
 kernel), (b) forward on [upsample(x0) | x1] (upsample-folded direct route), (c) the weight gradient (direct / folded / grouped
 Winograd).  `python r5_winograd_probe.py [dgrad] [fwd2] [wgrad]`; the weight gradient's staging variant is an environment knob
-read once per process (SEGSDE_WGRAD_FUSED_VAR = 0 / 1 / 2): run once per variant."""
+read once per process (SEGSDE_WGRAD_FUSED_VAR = 0 / 1): run once per variant."""
 import os
 import sys
 
@@ -37,7 +37,7 @@ def rnd(*shape):
 
 
 if "dgrad" in what:
-    print("# (a) data-gradient, mirrored padding, ELU derivative in the epilogue: direct reflection-adjoint kernel vs one-kernel Winograd + border launches")
+    print("# (a) data-gradient, mirrored padding, ELU derivative in the epilogue: direct reflection-adjoint kernel vs one-kernel Winograd + border kernel")
     for name, Hh, W, C, Co in [("128->64 @256x512", 256, 512, 128, 64), ("128->128 @128x256", 128, 256, 128, 128),
                                ("256->128 @64x128", 64, 128, 256, 128), ("256->256 @32x64", 32, 64, 256, 256),
                                ("64->64 @128x256 zero-pad (layer1)", 128, 256, 64, 64)]:
@@ -48,18 +48,15 @@ if "dgrad" in what:
         wfp, wdp = H.pack_weight_both(w)
         ud = H.winograd_fused_pack(w, True)
         ag = (a, "elu")
-        t_d = timed(lambda: H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag))
-        t_f1 = timed(lambda: H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag, wino=ud))      # border terms: implicit-GEMM border launches
+        t_d = timed(lambda: H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag, wino=None))      # the direct route
         t_f = timed(lambda: H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag, wino=ud, wfpack=wfp))   # border kernel (two launches)
-        H.WINO_FUSED_DGRAD_EXT = False
         t_fz = timed(lambda: H.winograd_fused("conv_dgrad", dy, ud))      # the zero-padded launch alone: what the borders + epilogue cost
-        H.WINO_FUSED_DGRAD_EXT = True
-        d1, _ = H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag)
+        d1, _ = H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag, wino=None)
         d2, _ = H.conv_dgrad(g, dy, wdp, w, (Hh, W), actgrad=ag, wino=ud, wfpack=wfp)
         err = float((d1 - d2).abs().max()) / float(d1.abs().max())
         gf = 2.0 * B * Hh * W * C * Co * 9 / 1e6
-        print("%-36s direct %7.1f us (%5.1f TF)  fused %7.1f us (%5.1f TF alg, %.2fx; with implicit-GEMM border launches %7.1f us; zero-padded launch alone, no derivative %7.1f us)  rel. diff %.1e"
-              % (name, t_d, gf / t_d, t_f, gf / t_f, t_d / t_f, t_f1, t_fz, err), flush=True)
+        print("%-36s direct %7.1f us (%5.1f TF)  fused %7.1f us (%5.1f TF alg, %.2fx; zero-padded launch alone, no derivative %7.1f us)  rel. diff %.1e"
+              % (name, t_d, gf / t_d, t_f, gf / t_f, t_d / t_f, t_fz, err), flush=True)
 
 if "fwd2" in what:
     print("# (b) forward on [upsample(x0) | x1], mirrored padding, bias + ELU: upsample-folded direct route vs one-kernel Winograd")

@@ -10,9 +10,5 @@ PY
 }
 run A=0
 run SEGSDE_WINO_FUSED_WGRAD=0
-run SEGSDE_WINO_FUSED_DGRAD_EXT=0
-run SEGSDE_WINO_FUSED2=0
-run SEGSDE_WINO_FUSED_DGRAD2=0
-run SEGSDE_WINO_FUSED_WGRAD=0 SEGSDE_WINO_FUSED_DGRAD_EXT=0 SEGSDE_WINO_FUSED2=0 SEGSDE_WINO_FUSED_DGRAD2=0
 run SEGSDE_BN_PARTIALS_WIDE_MAX=0
 run SEGSDE_WGRAD_FUSED_WGS=256
