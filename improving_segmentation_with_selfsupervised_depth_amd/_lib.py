@@ -9,7 +9,7 @@ from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -197,6 +197,10 @@ _SIGS = {
     "segsde_depth_errors_workspace": (c_size_t, [c_int, c_int, c_int]),
     "segsde_depth_errors": (c_int, [P, P, c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_int, c_int, c_int, c_int, P, P,
                                     c_size_t, P]),
+    "segsde_seg_eval_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "segsde_seg_eval_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "segsde_seg_eval": (c_int, [P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int64, P, P, P, P,
+                                c_size_t, P]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -556,19 +556,8 @@ __global__ __launch_bounds__(256) void upsample2x_fwd_kernel(const float* x, int
   }
 }
 
-// ------------------------------------------------------------------ bilinear resize (ATen upsample_bilinear2d semantics)
-struct Lerp { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Lerp lerp_src(int dst, int in, int out, int align_corners) {
-  float scale, src;
-  if (align_corners) { scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; src = scale * (float)dst; }
-  else { scale = (float)in / (float)out; src = scale * ((float)dst + 0.5f) - 0.5f; if (src < 0.f) src = 0.f; }
-  Lerp r;
-  r.i0 = (int)src; if (r.i0 > in - 1) r.i0 = in - 1;
-  r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-  r.l1 = src - (float)r.i0; r.l0 = 1.f - r.l1;
-  return r;
-}
-
+// ------------------------------------------------------------------ bilinear resize (ATen upsample_bilinear2d semantics;
+// Lerp / lerp_src: segsde_common.h)
 __global__ __launch_bounds__(256) void resize_fwd_kernel(const float* x, int ldx, int B, int Hi, int Wi, int C, float* y,
                                                          int ldy, int Ho, int Wo, int ac) {
   const long total = (long)B * Ho * Wo * C;

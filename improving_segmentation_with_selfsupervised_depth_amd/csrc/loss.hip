@@ -10,7 +10,6 @@
 namespace {
 #define ST(s) static_cast<hipStream_t>(s)
 
-struct Lerp { int i0, i1; float l0, l1; };
 // F.interpolate(..., mode="bilinear", align_corners=False) source coordinates (ATen area_pixel_compute_source_index)
 __device__ __forceinline__ Lerp lerp_half(int dst, int in, int out) {
   const float scale = (float)in / (float)out;

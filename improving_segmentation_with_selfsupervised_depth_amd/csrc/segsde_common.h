@@ -207,6 +207,21 @@ __device__ __forceinline__ float segsde_act_grad_from_out(float y, int act) {
   return 1.f;
 }
 
+// Source taps and weights of one destination index of a bilinear resize, ATen upsample_bilinear2d semantics
+// (area_pixel_compute_source_index): the value is l0 * x[i0] + l1 * x[i1] along this axis.  elementwise.hip (resize forward and
+// adjoint) and segeval.hip (validation at label resolution) share it, so that both interpolate bit for bit alike.
+struct Lerp { int i0, i1; float l0, l1; };
+__device__ __forceinline__ Lerp lerp_src(int dst, int in, int out, int align_corners) {
+  float scale, src;
+  if (align_corners) { scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; src = scale * (float)dst; }
+  else { scale = (float)in / (float)out; src = scale * ((float)dst + 0.5f) - 0.5f; if (src < 0.f) src = 0.f; }
+  Lerp r;
+  r.i0 = (int)src; if (r.i0 > in - 1) r.i0 = in - 1;
+  r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
+  r.l1 = src - (float)r.i0; r.l0 = 1.f - r.l1;
+  return r;
+}
+
 // counter-based RNG for dropout masks: the backward pass regenerates the mask from (seed, element index)
 __device__ __forceinline__ uint32_t segsde_hash32(uint64_t x) {
   x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;

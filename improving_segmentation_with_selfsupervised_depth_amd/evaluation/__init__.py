@@ -1,1 +1,1 @@
-from .metrics import runningDepthScore, runningScore  # noqa: F401
+from .metrics import AverageMeter, AverageMeterDict, runningDepthScore, runningScore  # noqa: F401

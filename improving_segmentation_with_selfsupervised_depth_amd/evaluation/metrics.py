@@ -47,9 +47,20 @@ class runningScore(object):
         for lt, lp in zip(label_trues, label_preds):
             self._host += self._fast_hist(lt.flatten(), lp.flatten(), self.n_classes)
 
-    def update_from_logits(self, label_trues, semantics):
-        """train.py:848-851 in one kernel: ``pred = semantics.data.max(1)[1]`` fused with the histogram"""
-        H.confusion_update(self._hist(semantics.device), label_trues.detach(), logits=semantics.detach())
+    def update_from_logits(self, label_trues, semantics, return_loss=False, return_ids=False):
+        """train.py:839-851 in one kernel: ``pred = semantics.data.max(1)[1]`` fused with the histogram.  Labels of another size
+        than the logits: the logits are interpolated to the label grid inside the kernel (``hipops.seg_eval``: the reference's
+        ``F.interpolate(..., mode="bilinear", align_corners=True)`` without the resized tensor).  ``return_loss``: also the value
+        of the reference's ``cross_entropy2d(input=semantics, target=label_trues)`` without class or pixel weights, its resize
+        included, from the same pass -- a 0-dim float32 tensor on the device, NaN when no pixel counts.  ``return_ids``: also the
+        prediction as a uint8 [B,Ht,Wt] plane.  Returns None, the loss, the ids, or (loss, ids).  No host synchronisation."""
+        if not (return_loss or return_ids) and tuple(label_trues.shape[-2:]) == tuple(semantics.shape[-2:]):
+            H.confusion_update(self._hist(semantics.device), label_trues.detach(), logits=semantics.detach())
+            return None
+        _, pair, ids = H.seg_eval(semantics.detach(), label_trues.detach(), hist=self._hist(semantics.device),
+                                  want_loss=return_loss, want_ids=return_ids)
+        loss = (pair[0] / pair[1]).float() if return_loss else None
+        return (loss, ids) if return_loss and return_ids else (loss if return_loss else ids)
 
     def get_scores(self):
         """metrics.py:27-56"""
@@ -109,3 +120,43 @@ class runningDepthScore(object):
 
     def reset(self):
         self._acc = None
+
+
+def _detached(v):
+    return v.detach() if torch.is_tensor(v) else v
+
+
+class AverageMeter(object):
+    """Running average with the attributes of the reference's meter (evaluation/metrics.py:58-76): ``val`` the last value, ``sum``
+    of ``val * n``, ``count`` of ``n``, ``avg = torch.true_divide(sum, count)``.  Device tensors stay on the device and the count
+    is a Python number, so an update never synchronises."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.val = self.avg = self.sum = self.count = 0
+
+    def update(self, val, n=1):
+        self.val = _detached(val)
+        self.sum = self.sum + self.val * n
+        self.count = self.count + n
+        self.avg = torch.true_divide(self.sum, self.count)
+
+
+class AverageMeterDict(object):
+    """One running average per key (the reference's evaluation/metrics.py:79-99): ``sums``, ``counts`` and ``avgs`` are dicts over
+    the keys seen so far; a key first seen later starts from zero then."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.avgs, self.sums, self.counts = {}, {}, {}
+
+    def update(self, vals, n=1):
+        for key, v in vals.items():
+            total = self.sums.get(key, 0) + _detached(v) * n
+            seen = self.counts.get(key, 0) + n
+            self.sums[key], self.counts[key] = total, seen
+            self.avgs[key] = torch.true_divide(total, seen)

@@ -2310,3 +2310,53 @@ def depth_errors(gt, pred, min_depth=1e-3, max_depth=80.0, median_scaling=True, 
         _p(gt), _p(pred), B, Hh, W, float(min_depth), float(max_depth), int(bool(median_scaling)), float(scale), y0, y1, x0, x1,
         _p(table), _p(ws_), nb, _stream(gt)), "depth_errors"))
     return table
+
+
+# ----------------------------------------------------------------------------------------------
+# segmentation validation at label resolution (csrc/segeval.hip; evaluation/metrics.py::runningScore.update_from_logits and
+# trainer.validate call it)
+# ----------------------------------------------------------------------------------------------
+def seg_eval(logits, gt, n_classes=None, hist=None, ignore_index=250, want_loss=True, want_ids=False):
+    """logits [B,C,Hi,Wi] (NCHW-logical; dense, channels-last or a slice: read in place through its strides), gt int64 [B,Ht,Wt] of any
+    size -> (hist, loss_pair, ids).  Per label pixel: the logits interpolated bilinearly (align_corners=True) to the label grid,
+    their argmax (lowest index on a tie), ``hist[C * gt + argmax] += 1`` into the int64 [C*C] ``hist`` (a fresh zero one when None and
+    ``n_classes`` is given; None back when neither is), the cross-entropy sum and pixel count over ``gt != ignore_index`` as a
+    float64 [2] (``want_loss``), the argmax as a uint8 [B,Ht,Wt] plane (``want_ids``).  The resized logits are never materialised; no
+    host synchronisation; two calls on the same input return the same bits."""
+    if not (torch.is_tensor(logits) and logits.dim() == 4 and logits.is_floating_point()):
+        raise TypeError("logits must be a floating-point [B,C,Hi,Wi] tensor")
+    if not (torch.is_tensor(gt) and gt.dim() == 3 and gt.dtype == torch.int64):
+        raise TypeError("gt must be an int64 [B,Ht,Wt] tensor")
+    if gt.shape[0] != logits.shape[0]:
+        raise ValueError("logits hold %d images, gt %d" % (logits.shape[0], gt.shape[0]))
+    if gt.device != logits.device:
+        raise ValueError("logits are on %s, gt on %s" % (logits.device, gt.device))
+    B, C, Hi, Wi = (int(s) for s in logits.shape)
+    Ht, Wt = int(gt.shape[1]), int(gt.shape[2])
+    if min(B, C, Hi, Wi, Ht, Wt) < 1:
+        raise ValueError("empty logits %s or labels %s" % (tuple(logits.shape), tuple(gt.shape)))
+    if n_classes is not None and int(n_classes) != C:
+        raise ValueError("n_classes = %d, but the logits have %d classes" % (n_classes, C))
+    if hist is not None:
+        if not (torch.is_tensor(hist) and hist.dtype == torch.int64 and hist.numel() == C * C and hist.is_contiguous()):
+            raise ValueError("hist must be a contiguous int64 tensor of %d x %d elements" % (C, C))
+        if hist.device != logits.device:
+            raise ValueError("hist is on %s, logits on %s" % (hist.device, logits.device))
+    elif n_classes is not None:
+        hist = torch.zeros(C * C, dtype=torch.int64, device=logits.device)
+    if want_ids and C > 256:
+        raise ValueError("ids are uint8: at most 256 classes, got %d" % C)
+    if hist is None and not want_loss and not want_ids:
+        raise ValueError("nothing to compute: no hist (or n_classes), want_loss and want_ids are off")
+    lg, gt = logits.detach().float(), gt.detach().contiguous()
+    pair = torch.empty(2, dtype=torch.float64, device=lg.device) if want_loss else None
+    ids = torch.empty((B, Ht, Wt), dtype=torch.uint8, device=lg.device) if want_ids else None
+    L = _lib.lib()
+    nb = L.segsde_seg_eval_workspace(B, Ht, Wt) if want_loss else 0
+    ws_ = _ws(nb, lg) if want_loss else None
+    sb, sc, sh, sw = lg.stride()
+    nbytes = 4.0 * B * C * Hi * Wi + B * Ht * Wt * (8.0 + (1.0 if want_ids else 0.0))
+    _timed("hbm_seg_eval", nbytes, lg, lambda: check(L.segsde_seg_eval(
+        _p(lg), sb, sc, sh, sw, B, C, Hi, Wi, _p(gt), Ht, Wt, int(ignore_index), _p(hist), _p(pair), _p(ids), _p(ws_), nb,
+        _stream(lg)), "seg_eval"))
+    return hist, pair, ids

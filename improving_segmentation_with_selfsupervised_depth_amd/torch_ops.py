@@ -241,6 +241,17 @@ def depth_errors(gt, pred, min_depth=1e-3, max_depth=80.0, median_scaling=True, 
                           None if crop is None else tuple(int(c) for c in crop))
 
 
+# ----------------------------------------------------------------------------------------------- segmentation validation
+@_op("seg_eval(Tensor logits, Tensor gt, int ignore_index=250, bool want_loss=True, bool want_ids=False) -> (Tensor, Tensor?, Tensor?)")
+def seg_eval(logits, gt, ignore_index=250, want_loss=True, want_ids=False):
+    """logits [B,C,Hi,Wi], int64 labels [B,Ht,Wt] of any size -> (int64 [C*C] confusion counts of this call, float64 [2] cross-entropy
+    sum and pixel count or None, uint8 [B,Ht,Wt] argmax or None), all at label resolution without the resized logits
+    (hipops.seg_eval with a fresh histogram; forward only)"""
+    _forward_only("seg_eval", logits)
+    return H.seg_eval(logits.detach(), gt, n_classes=int(logits.shape[1]), ignore_index=int(ignore_index),
+                      want_loss=bool(want_loss), want_ids=bool(want_ids))
+
+
 def names():
     """qualified names of everything registered above"""
     return ["%s::%s" % (NAMESPACE, n) for n in SCHEMAS]

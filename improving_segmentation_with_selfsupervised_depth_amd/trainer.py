@@ -452,3 +452,110 @@ def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calc
             "pseudo_depth_loss": pseudo_depth_loss.detach(), "feat_dist_loss": feat_dist_loss.detach(),
             "segmentation_total_loss": segmentation_total.detach(), "mono_total_loss": mono_total.detach(),
             "total_loss": total.detach()}
+
+
+def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=None, loss_fn=None, running_depth=None,
+             n_imgs_to_save=None, device=None):
+    """``Trainer.validate`` (train.py:817-902) as a free function over what the method reads from ``self``; no writer.
+    ``val_batches``: an iterable of input dicts (the validation loader).  The model runs in ``eval()`` mode (the previous mode is
+    restored on return) under ``no_grad`` and ``autocast(enabled=cfg["training"]["amp"])``.
+
+    Segmentation (train.py:836-851): with ``loss_fn`` None or this package's ``cross_entropy2d`` the loss, the prediction and the
+    confusion matrix come from ONE pass of ``runningScore.update_from_logits(..., return_loss=True)`` at the labels' resolution --
+    whenever the two sizes differ the logits are interpolated inside the kernel (the reference resizes under ``h != ht and w !=
+    wt``, a subset); a custom ``loss_fn`` is called as the reference calls it and the matrix follows from ``update_from_logits``.
+    Monodepth (train.py:857-868) and the BerHu pseudo-depth term with the own-car crop (train.py:870-878) as in the reference.
+    ``running_depth`` (a ``runningDepthScore``) is updated with outputs[("depth", 0, 0)] when the batch has "depth_gt".
+    ``n_imgs_to_save`` defaults to ``cfg["training"]["n_tensorboard_imgs"]``.
+
+    -> {"losses": {name: float}, "score": ..., "class_iou": ... (``runningScore.get_scores``; None without segmentation),
+    "depth": ``running_depth.get_scores()`` or None, "imgs_to_save": [[img, label, pred_ids, disp], ...] (device tensors, the
+    prediction a uint8 plane at label size)}.  Nothing is copied to the host inside the loop."""
+    from .evaluation.metrics import AverageMeterDict, runningScore
+    from .loss.loss import berhu
+    tr = cfg["training"]
+    if device is None:
+        device = next(model.parameters()).device
+    if n_imgs_to_save is None:
+        n_imgs_to_save = tr.get("n_tensorboard_imgs", 0)
+    fused_loss = loss_fn is None or loss_fn is cross_entropy2d
+    was_training = model.training
+    model.eval()
+    val_loss_meter = AverageMeterDict()
+    running_metrics_val = runningScore(n_classes)
+    imgs_to_save = []
+    zero = torch.tensor(0)
+    try:
+        with torch.no_grad():
+            for inputs_val in val_batches:
+                required_inputs = [("color_aug", 0, 0), "lbl"] if cfg["model"]["disable_monodepth"] else inputs_val.keys()
+                for k, v in inputs_val.items():
+                    if torch.is_tensor(v) and k in required_inputs:
+                        inputs_val[k] = v.to(device, non_blocking=True)
+                images_val = inputs_val[("color_aug", 0, 0)]
+                with torch.autocast(device_type="cuda", enabled=bool(tr.get("amp", False))):
+                    outputs = model(inputs_val)
+
+                if tr["segmentation_lambda"] > 0:
+                    labels_val = inputs_val["lbl"]
+                    semantics = outputs["semantics"]
+                    want_ids = len(imgs_to_save) < n_imgs_to_save
+                    if not fused_loss:
+                        val_segmentation_loss = loss_fn(input=semantics, target=labels_val)
+                    got = running_metrics_val.update_from_logits(labels_val, semantics, return_loss=fused_loss, return_ids=want_ids)
+                    if fused_loss:
+                        val_segmentation_loss = got[0] if want_ids else got
+                    pred = (got[1] if fused_loss else got) if want_ids else [None] * images_val.shape[0]
+                    gt = labels_val
+                else:
+                    pred = [None] * images_val.shape[0]
+                    gt = [None] * images_val.shape[0]
+                    val_segmentation_loss = zero
+
+                if not cfg["model"]["disable_monodepth"]:
+                    if not cfg["model"]["disable_pose"]:
+                        monodepth_loss_calculator_val.generate_images_pred(inputs_val, outputs)
+                        val_mono_loss = monodepth_loss_calculator_val.compute_losses(inputs_val, outputs)["loss"]
+                    else:
+                        outputs.update(model.predict_test_disp(inputs_val))
+                        monodepth_loss_calculator_val.generate_depth_test_pred(outputs)
+                        val_mono_loss = zero
+                    if running_depth is not None and "depth_gt" in inputs_val:
+                        depth_gt = inputs_val["depth_gt"]
+                        depth = outputs[("depth", 0, 0)].detach()
+                        if depth.dim() == 3:
+                            depth = depth[:, None]
+                        if tuple(depth.shape[-2:]) != tuple(depth_gt.shape[-2:]):      # as MonodepthLoss.compute_depth_metrics
+                            depth = H.resize_bilinear(depth.float().contiguous().permute(0, 2, 3, 1), tuple(depth_gt.shape[-2:]),
+                                                      False).permute(0, 3, 1, 2)
+                        running_depth.update(depth_gt, depth)
+                else:
+                    outputs[("disp", 0)] = [None] * images_val.shape[0]
+                    val_mono_loss = zero
+
+                if cfg["data"].get("depth_teacher", None) is not None:
+                    # crop away the bottom of the image with the own car
+                    depth_loss_mask = torch.ones(outputs["disp", 0].shape, device=device)
+                    depth_loss_mask[:, :, int(outputs["disp", 0].shape[2] * 0.9):, :] = 0
+                    val_pseudo_depth_loss = berhu(outputs["disp", 0], inputs_val["pseudo_depth"], depth_loss_mask,
+                                                  apply_log=tr.get("pseudo_depth_loss_log", False))
+                else:
+                    val_pseudo_depth_loss = zero
+
+                val_loss_meter.update({"segmentation_loss": val_segmentation_loss.detach(),
+                                       "monodepth_loss": val_mono_loss.detach(),
+                                       "pseudo_depth_loss": val_pseudo_depth_loss.detach()})
+
+                for img, label, output, depth in zip(images_val, gt, pred, outputs[("disp", 0)]):
+                    if len(imgs_to_save) < n_imgs_to_save:
+                        imgs_to_save.append([img, label, output, depth if depth is None else depth.detach()])
+    finally:
+        model.train(was_training)
+
+    result = {"losses": {k: float(v) for k, v in val_loss_meter.avgs.items()}, "score": None, "class_iou": None,
+              "depth": None, "imgs_to_save": imgs_to_save}
+    if tr["segmentation_lambda"] > 0:
+        result["score"], result["class_iou"] = running_metrics_val.get_scores()
+    if running_depth is not None:
+        result["depth"] = running_depth.get_scores()
+    return result

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 24
+#define SEGSDE_ABI_VERSION 25
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -765,6 +765,32 @@ size_t segsde_depth_errors_workspace(int B, int H, int W);
 int segsde_depth_errors(const float* gt, const float* pred, int B, int H, int W, float min_depth, float max_depth,
                         int median_scaling, float scale, int y0, int y1, int x0, int x1, double* table, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ---- segmentation validation at label resolution (train.py:836-851 with loss.py:17-37 as the loss), csrc/segeval.hip.
+ * logits: float32 [B,C,Hi,Wi] on the device addressed by four ELEMENT strides (batch, class, row, pixel): dense NCHW,
+ * channels-last and slices need no copy; the batch and class offsets are 64-bit.  labels: dense int64 [B,Ht,Wt], any Hi,Wi ->
+ * Ht,Wt ratio.  For every label pixel the C logits are interpolated as F.interpolate(mode="bilinear", align_corners=True) does in
+ * fp32 (the arithmetic of segsde_resize_bilinear_forward, bit for bit), then
+ *   argmax over the classes: strict >, the lowest index wins a tie (segsde_confusion_update's rule; NaN logits: unspecified);
+ *   hist[C * label + argmax] += 1                                    where 0 <= label < C          (hist: [C*C], ACCUMULATED);
+ *   loss[0] += logsumexp(z) - z[label], loss[1] += 1                 where label != ignore_index and 0 <= label < C
+ *                                                                    (fp32 with the maximum subtracted, summed in float64;
+ *                                                                    loss: double[2], OVERWRITTEN);
+ *   ids[pixel] = argmax                                              (uint8 [B,Ht,Wt]).
+ * Each of hist, loss, ids may be null (not all three).  A label outside [0,C) other than ignore_index counts nowhere.
+ * One launch (plus a one-block fold of the loss partials), no host synchronisation.  Block-private histograms with integer
+ * atomics and block partials folded in a fixed order: two calls give identical bits.
+ * SEGSDE_ERR_NULL: logits, labels, all three outputs, or loss without a workspace.  SEGSDE_ERR_SHAPE: B, C, Hi, Wi, Ht, Wt <= 0.
+ * SEGSDE_ERR_UNSUPPORTED: a C whose C*C histogram leaves no room for a tile in 64 KB of LDS (C <= 125 works), C > 256 with ids,
+ * Ht * Wt >= 2^32, more than 2^31 - 1 tiles, a workspace that is not 8-byte aligned.  SEGSDE_ERR_WORKSPACE: loss asked for and
+ * fewer than segsde_seg_eval_workspace(B, Ht, Wt) bytes.
+ * segsde_seg_eval_plan: the label rows per tile (16, 8 or 4; tiles are 64 pixels wide) when the tile's source footprint is staged
+ * in LDS, 0 when the taps are read straight from memory (the footprint fits at no tile height), or an error code as above. */
+size_t segsde_seg_eval_workspace(int B, int Ht, int Wt);
+int segsde_seg_eval_plan(int C, int Hi, int Wi, int Ht, int Wt);
+int segsde_seg_eval(const float* logits, long sb, long sc, long sh, long sw, int B, int C, int Hi, int Wi, const int64_t* labels,
+                    int Ht, int Wt, int64_t ignore_index, unsigned long long* hist, double* loss, unsigned char* ids,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
