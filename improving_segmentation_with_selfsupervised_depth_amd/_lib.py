@@ -5,11 +5,11 @@ the shared object is missing, or a tensor that is not on the GPU reaches an op, 
 """
 import ctypes
 import os
-from ctypes import c_int, c_long, c_float, c_void_p, c_size_t, c_uint64, c_int64, POINTER
+from ctypes import c_int, c_long, c_float, c_double, c_void_p, c_size_t, c_uint64, c_int64, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGSDE_LIB") or os.path.join(_HERE, "libsegsde_hip.so")   # override: kernel experiments
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _LIB = None
 # Set only by the test-suite when it injects the host-interpreted build of the same kernel sources
@@ -201,6 +201,9 @@ _SIGS = {
     "segsde_seg_eval_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "segsde_seg_eval": (c_int, [P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int64, P, P, P, P,
                                 c_size_t, P]),
+    "segsde_berhu_workspace": (c_size_t, [c_long]),
+    "segsde_berhu_forward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, c_double, P, P, P, c_size_t, P]),
+    "segsde_berhu_backward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, P, P, P, P]),
 }
 EXPORTS = sorted(_SIGS)
 

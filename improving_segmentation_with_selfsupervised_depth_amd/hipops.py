@@ -2360,3 +2360,71 @@ def seg_eval(logits, gt, n_classes=None, hist=None, ignore_index=250, want_loss=
         _p(lg), sb, sc, sh, sw, B, C, Hi, Wi, _p(gt), Ht, Wt, int(ignore_index), _p(hist), _p(pair), _p(ids), _p(ws_), nb,
         _stream(lg)), "seg_eval"))
     return hist, pair, ids
+
+
+# ----------------------------------------------------------------------------------------------
+# BerHu pseudo-depth loss (csrc/berhu.hip; loss.loss.berhu / berhu_own_car call it)
+# ----------------------------------------------------------------------------------------------
+BERHU_THRESHOLD = 0.2         # the reference's constant (loss.py:6)
+
+
+def _berhu_operands(input, target, mask, keep_rows):
+    """-> (x, t, m or None, n, H, W, keep_rows or -1): float32, broadcast to one shape, dense"""
+    for name, v in (("input", input), ("target", target), ("mask", mask)):
+        if v is not None and not (torch.is_tensor(v) and v.is_floating_point()):
+            raise TypeError("%s must be a floating-point tensor" % name)
+    ops = [input.detach().float(), target.detach().float()] + ([] if mask is None else [mask.detach().float()])
+    if any(o.device != ops[0].device for o in ops):
+        raise ValueError("input, target and mask are on different devices: %s" % ", ".join(str(o.device) for o in ops))
+    ops = [o.contiguous() for o in torch.broadcast_tensors(*ops)]
+    x = ops[0]
+    if x.numel() < 1:
+        raise ValueError("empty operands %s" % (tuple(x.shape),))
+    Hh = W = 0
+    if keep_rows is None:
+        keep_rows = -1
+    else:
+        if x.dim() < 2:
+            raise ValueError("keep_rows needs operands of at least two dimensions [.., H, W], got %s" % (tuple(x.shape),))
+        Hh, W, keep_rows = int(x.shape[-2]), int(x.shape[-1]), int(keep_rows)
+        if not 0 <= keep_rows <= Hh:
+            raise ValueError("keep_rows = %d outside [0, %d]" % (keep_rows, Hh))
+    return x, ops[1], (ops[2] if mask is not None else None), x.numel(), Hh, W, keep_rows
+
+
+def berhu_forward(input, target, mask=None, keep_rows=None, apply_log=False):
+    """BerHu loss of loss.py:5-15 -> (loss float32 [1], state float32 [2] = {max a, C}) on the device, a = |target - input| * mask
+    (log(1 + .) of both first with ``apply_log``), C = 0.2 max a, loss = mean over every element of a where a <= C, else
+    (a^2 + C^2) / (2 C).  ``keep_rows``: rows >= keep_rows of the last-but-one dimension count as masked (the own-car crop) without
+    a mask tensor; it combines with ``mask``.  Operands: float32 (other float dtypes are converted), broadcast against each other
+    with ``torch.broadcast_tensors``; an operand that is not dense afterwards (a broadcast mask, a slice with gaps) costs one
+    contiguous copy.  No host synchronisation; max a == 0 gives loss 0 (and a zero gradient, where the reference has NaN)."""
+    x, t, m, n, Hh, W, kr = _berhu_operands(input, target, mask, keep_rows)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    state = torch.empty(2, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    nb = L.segsde_berhu_workspace(n)
+    ws_ = _ws(nb, x)
+    nbytes = 2.0 * n * (8.0 + (4.0 if m is not None else 0.0))
+    _timed("hbm_berhu", nbytes, x, lambda: check(L.segsde_berhu_forward(
+        _p(x), _p(t), _p(m), n, Hh, W, kr, int(bool(apply_log)), BERHU_THRESHOLD, _p(loss), _p(state), _p(ws_), nb, _stream(x)),
+        "berhu_forward"), "fwd")
+    return loss, state
+
+
+def berhu_backward(input, target, state, gscale, mask=None, keep_rows=None, apply_log=False):
+    """d loss / d input of ``berhu_forward`` (same operands, its ``state``) times the DEVICE scalar ``gscale`` (float32, one element)
+    -> float32 tensor of the broadcast shape; exactly 0 at masked, cropped and target == input elements.  One launch."""
+    x, t, m, n, Hh, W, kr = _berhu_operands(input, target, mask, keep_rows)
+    if not (torch.is_tensor(state) and state.dtype == torch.float32 and state.numel() == 2 and state.is_contiguous()):
+        raise ValueError("state must be the float32 [2] tensor berhu_forward returned")
+    if not (torch.is_tensor(gscale) and gscale.numel() == 1):
+        raise ValueError("gscale must be a one-element tensor")
+    if state.device != x.device or gscale.device != x.device:
+        raise ValueError("state / gscale are not on the operands' device %s" % x.device)
+    g = _f32(gscale, "gscale").reshape(1)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    nbytes = n * (12.0 + (4.0 if m is not None else 0.0))
+    _timed("hbm_berhu", nbytes, x, lambda: check(_lib.lib().segsde_berhu_backward(
+        _p(x), _p(t), _p(m), n, Hh, W, kr, int(bool(apply_log)), _p(state), _p(g), _p(dx), _stream(x)), "berhu_backward"), "bwd")
+    return dx

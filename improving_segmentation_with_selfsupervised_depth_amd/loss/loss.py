@@ -47,14 +47,55 @@ def cross_entropy2d(input, target, class_weight=None, pixel_weights=None):
     return _CrossEntropyFn.apply(x, target.reshape(-1), class_weight, pixel_weights, mean_over_all)
 
 
+class _BerHuFn(Fn.Function):
+    """hipops.berhu_forward / berhu_backward (csrc/berhu.hip).  Nothing but the operands and the two floats {max, C} is kept for the
+    backward pass, which recomputes; the gradient goes to ``input`` only."""
+
+    @staticmethod
+    def forward(ctx, input, target, mask, keep_rows, apply_log):
+        loss, state = H.berhu_forward(input, target, mask, keep_rows, apply_log)
+        ctx.save_for_backward(input, target, mask, state)
+        ctx.keep_rows, ctx.apply_log = keep_rows, apply_log
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        input, target, mask, state = ctx.saved_tensors
+        dx = H.berhu_backward(input, target, state, g.detach().float().reshape(1), mask, ctx.keep_rows, ctx.apply_log)
+        if dx.shape != input.shape:           # input was broadcast against a larger target / mask
+            dx = dx.sum_to_size(input.shape)
+        return dx.to(input.dtype), None, None, None, None
+
+
+def _berhu(input, target, mask, keep_rows, apply_log):
+    if not torch.is_tensor(input) or not torch.is_tensor(target):
+        raise TypeError("berhu: input and target must be tensors")
+    if mask is not None and not torch.is_tensor(mask):
+        mask = torch.as_tensor(mask, dtype=torch.float32, device=input.device)
+    if torch.is_grad_enabled() and (target.requires_grad or (mask is not None and mask.requires_grad)):
+        raise NotImplementedError("berhu: the gradient goes to `input` only; detach the target and the mask")
+    return _BerHuFn.apply(input, target, mask, keep_rows, bool(apply_log))
+
+
+@Fn.fp32_region
 def berhu(input, target, mask, apply_log=False):
-    """reference loss.py:5-15 (pseudo-depth distillation; off in every benchmark config).  Plain torch ops."""
-    threshold = 0.2
-    if apply_log:
-        input, target = torch.log(1 + input), torch.log(1 + target)
-    absdiff = torch.abs(target - input) * mask
-    C = threshold * torch.max(absdiff).item()
-    return torch.mean(torch.where(absdiff <= C, absdiff, (absdiff * absdiff + C * C) / (2 * C)))
+    """reference loss.py:5-15, the pseudo-depth distillation loss: a = |target - input| * mask (log(1 + .) of both first with
+    ``apply_log``), C = 0.2 max(a), mean over every element of a where a <= C, else (a^2 + C^2) / (2 C) -> 0-dim tensor on the
+    device.  Three HIP launches forward, one backward, and no host synchronisation: the reference's read of the maximum on the host
+    is gone, C stays on the device (a constant for the gradient, as the reference's detached float is).  The gradient goes to
+    ``input`` only: a ``target`` or ``mask`` that requires grad raises NotImplementedError.  The operands are broadcast against
+    each other; one that is not dense float32 afterwards costs a copy.
+    Deviation: when max(a) == 0 (target == input on every unmasked element) the loss is 0 and the gradient all zeros; the
+    reference returns NaN gradients there (the 0/0 of ``torch.where``'s unselected branch).  NaN inputs are unspecified."""
+    return _berhu(input, target, mask, None, apply_log)
+
+
+@Fn.fp32_region
+def berhu_own_car(input, target, apply_log=False, keep=0.9):
+    """``berhu`` with the mask both callers build (train.py:491-494, 871-874: ones with the rows from ``int(H * 0.9)`` on zeroed,
+    the ego vehicle at the bottom of the frame) derived from the element index inside the kernels: no mask tensor is allocated
+    or read.  ``input``: [.., H, W]; bit for bit the result of ``berhu`` with that mask."""
+    return _berhu(input, target, None, int(input.shape[-2] * keep), apply_log)
 
 
 def pixel_wise_entropy(logits, normalize=False):

@@ -252,6 +252,15 @@ def seg_eval(logits, gt, ignore_index=250, want_loss=True, want_ids=False):
                       want_loss=bool(want_loss), want_ids=bool(want_ids))
 
 
+# ----------------------------------------------------------------------------------------------- pseudo-depth distillation
+@_op("berhu(Tensor input, Tensor target, Tensor? mask=None, int? keep_rows=None, bool apply_log=False) -> Tensor")
+def berhu(input, target, mask=None, keep_rows=None, apply_log=False):
+    """loss/loss.py:5-15 with C = 0.2 max kept on the device -> 0-dim loss; ``keep_rows``: rows from there on do not count (the
+    own-car crop without a mask tensor).  The gradient goes to ``input`` (loss.loss.berhu's autograd Function)"""
+    from .loss.loss import _berhu
+    return _berhu(input, target, mask, None if keep_rows is None else int(keep_rows), bool(apply_log))
+
+
 def names():
     """qualified names of everything registered above"""
     return ["%s::%s" % (NAMESPACE, n) for n in SCHEMAS]

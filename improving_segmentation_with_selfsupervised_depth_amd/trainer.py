@@ -341,7 +341,7 @@ def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calc
     ``reducer`` (ddp.GradAllReducer): every backward but the step's last runs under ``no_sync()`` and ``finish()`` is called
     before the clipping."""
     import contextlib
-    from .loss.loss import berhu, feature_distance
+    from .loss.loss import berhu_own_car, feature_distance
     tr = cfg["training"]
     amp = bool(tr.get("amp", False))
     if scaler is None:
@@ -397,10 +397,8 @@ def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calc
         with hold(not (do_pd or do_seg)):
             scaler.scale(mono_total).backward(retain_graph=True)
     if do_pd:
-        with torch.no_grad():      # the bottom tenth of the frame (the ego vehicle) does not count, train.py:491-494
-            keep = torch.ones(outputs["disp", 0].shape, device=dev)
-            keep[:, :, int(outputs["disp", 0].shape[2] * 0.9):, :] = 0
-        pseudo_depth_loss = berhu(outputs["disp", 0], inputs["pseudo_depth"], keep) * tr["pseudo_depth_lambda"]
+        # the bottom tenth of the frame (the ego vehicle) does not count, train.py:491-494: the kernels derive that mask from the row
+        pseudo_depth_loss = berhu_own_car(outputs["disp", 0], inputs["pseudo_depth"]) * tr["pseudo_depth_lambda"]
         with hold(not do_seg):
             scaler.scale(pseudo_depth_loss).backward(retain_graph=True)
     if do_seg:
@@ -464,7 +462,8 @@ def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=N
     confusion matrix come from ONE pass of ``runningScore.update_from_logits(..., return_loss=True)`` at the labels' resolution --
     whenever the two sizes differ the logits are interpolated inside the kernel (the reference resizes under ``h != ht and w !=
     wt``, a subset); a custom ``loss_fn`` is called as the reference calls it and the matrix follows from ``update_from_logits``.
-    Monodepth (train.py:857-868) and the BerHu pseudo-depth term with the own-car crop (train.py:870-878) as in the reference.
+    Monodepth (train.py:857-868) as in the reference; the BerHu pseudo-depth term with the own-car crop (train.py:870-878) is
+    ``loss.berhu_own_car``: no mask tensor, its threshold stays on the device.
     ``running_depth`` (a ``runningDepthScore``) is updated with outputs[("depth", 0, 0)] when the batch has "depth_gt".
     ``n_imgs_to_save`` defaults to ``cfg["training"]["n_tensorboard_imgs"]``.
 
@@ -472,7 +471,7 @@ def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=N
     "depth": ``running_depth.get_scores()`` or None, "imgs_to_save": [[img, label, pred_ids, disp], ...] (device tensors, the
     prediction a uint8 plane at label size)}.  Nothing is copied to the host inside the loop."""
     from .evaluation.metrics import AverageMeterDict, runningScore
-    from .loss.loss import berhu
+    from .loss.loss import berhu_own_car
     tr = cfg["training"]
     if device is None:
         device = next(model.parameters()).device
@@ -534,11 +533,9 @@ def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=N
                     val_mono_loss = zero
 
                 if cfg["data"].get("depth_teacher", None) is not None:
-                    # crop away the bottom of the image with the own car
-                    depth_loss_mask = torch.ones(outputs["disp", 0].shape, device=device)
-                    depth_loss_mask[:, :, int(outputs["disp", 0].shape[2] * 0.9):, :] = 0
-                    val_pseudo_depth_loss = berhu(outputs["disp", 0], inputs_val["pseudo_depth"], depth_loss_mask,
-                                                  apply_log=tr.get("pseudo_depth_loss_log", False))
+                    # crop away the bottom of the image with the own car (no mask tensor: the kernels work it out from the row)
+                    val_pseudo_depth_loss = berhu_own_car(outputs["disp", 0], inputs_val["pseudo_depth"],
+                                                          apply_log=tr.get("pseudo_depth_loss_log", False))
                 else:
                     val_pseudo_depth_loss = zero
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SEGSDE_ABI_VERSION 25
+#define SEGSDE_ABI_VERSION 26
 
 enum { SEGSDE_ERR_NULL = -1, SEGSDE_ERR_SHAPE = -2, SEGSDE_ERR_WORKSPACE = -3, SEGSDE_ERR_UNSUPPORTED = -4 };
 enum { SEGSDE_ACT_NONE = 0, SEGSDE_ACT_RELU = 1, SEGSDE_ACT_ELU = 2, SEGSDE_ACT_SIGMOID = 3 };
@@ -791,6 +791,30 @@ int segsde_seg_eval_plan(int C, int Hi, int Wi, int Ht, int Wt);
 int segsde_seg_eval(const float* logits, long sb, long sc, long sh, long sw, int B, int C, int Hi, int Wi, const int64_t* labels,
                     int Ht, int Wt, int64_t ignore_index, unsigned long long* hist, double* loss, unsigned char* ids,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- BerHu pseudo-depth distillation loss (loss.py:5-15; the depth loss of experiments.py:229-301 and a term of every DepthMix
+ * validation, train.py:489-496, 870-878), csrc/berhu.hip.  input, target, mask: dense float32 tensors of n elements on the device
+ * (mask may be null: all ones).  With apply_log, input and target are replaced by log(1 + .) first.
+ *   a = |target - input| * mask * keep,  keep = 1, or with keep_rows >= 0 (the tensors are [.., H, W], H * W divides n): 1 where the
+ *   element's row (e / W) % H is < keep_rows, else 0 -- the own-car crop of both callers without a mask tensor;
+ *   C = float32(threshold * double(max a));
+ *   loss[0] = sum over ALL n elements of (a <= C ? a : (a * a + C * C) / (2 * C)), per element in fp32, summed in double, / n;
+ *   state[0] = max a (bit for bit the fp32 maximum), state[1] = C: kept for the backward pass.
+ * Backward: dinput = gscale[0] / n * -sign(target - input) * mask * keep * (a <= C ? 1 : a / C), divided by (1 + input) with
+ * apply_log; gscale is a DEVICE scalar (the incoming gradient), C a constant as in the reference (it detaches C with .item());
+ * exactly 0 wherever a == 0.  max a == 0 gives loss 0 and an all-zero gradient (the reference returns NaN gradients there, the
+ * 0/0 of torch.where's unselected branch).  NaN inputs: unspecified.
+ * Forward: three launches (block maxima; C and block sums in double; a fixed-order fold), backward: one; no host synchronisation,
+ * no atomics: two calls give identical bits.  16-byte accesses when every tensor starts on a 16-byte boundary.
+ * SEGSDE_ERR_SHAPE: n <= 0, keep_rows < -1, with keep_rows >= 0: H, W <= 0, keep_rows > H or n % (H * W) != 0 (H, W are not read
+ * otherwise), !(0 < threshold < inf).  SEGSDE_ERR_WORKSPACE: fewer than the workspace function's bytes.  SEGSDE_ERR_UNSUPPORTED:
+ * a tensor that is not 4-byte aligned, a workspace that is not 8-byte aligned. */
+size_t segsde_berhu_workspace(long n);
+int segsde_berhu_forward(const float* input, const float* target, const float* mask, long n, int H, int W, int keep_rows,
+                         int apply_log, double threshold, float* loss, float* state, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int segsde_berhu_backward(const float* input, const float* target, const float* mask, long n, int H, int W, int keep_rows,
+                          int apply_log, const float* state, const float* gscale, float* dinput, void* stream);
 
 #ifdef __cplusplus
 }
