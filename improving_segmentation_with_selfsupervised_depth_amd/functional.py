@@ -246,31 +246,28 @@ class ConvFn(Function):
         # Winograd route (3x3 / stride 1 / many channels): the transformed weight packs, cached by the owning module for the
         # active weight_pack_scope like the plain packs
         ctx.wino = None
-        # kn: the one-kernel Winograd route (64 .. 256 channels, one source) and its [16][K][N] packs; otherwise the grouped-GEMM
-        # route from 256 channels on (two sources, dilation, 512 channels)
-        # (round 5: the one-kernel route also takes the decoder's [upsample(x0) | x1] layers, forward only)
+        # the one-kernel route (64 .. 256 channels, one source or [upsample(x0) | x1]) and its [16][K][N] packs -- which the
+        # skip-source data-gradient of the two-source layers wants whatever route the forward takes -- or the grouped-GEMM route
+        # from 256 channels on (two sources, dilation, 512 channels): hipops.forward_routes, asked once
         up_f = 2 if g.up0 else 1
-        kn = H.winograd_fused_ok(g, x0.shape[0], x0.shape[1] * up_f, x0.shape[2] * up_f)
-        # (and, whatever route the forward takes, the skip-source data-gradient of the two-source layers: the flipped pack)
-        kn_d2 = (x1 is not None and g.up0 and (ctx.needs_input_grad[1])
-                 and H.winograd_fused_dgrad2_ok(g, x0.shape[0], x0.shape[1] * up_f, x0.shape[2] * up_f))
-        if kn or kn_d2 or (not g.up0 and H.winograd_ok(g, x0.shape[0], x0.shape[1], x0.shape[2])):
-            knl = kn or kn_d2                              # pack layout: [16][K][N] of the one-kernel route
+        ctx.in_hw = (x0.shape[1] * up_f, x0.shape[2] * up_f)
+        routes = H.forward_routes(g, x0.shape[0], ctx.in_hw[0], ctx.in_hw[1], skip_grad=x1 is not None and ctx.needs_input_grad[1])
+        if routes.kn_pack or routes.grouped:
             if (wino_cache is not None and wino_cache.get("key") is not None and wino_cache.get("key") == wino_cache.get("want")
-                    and bool(wino_cache.get("kn")) == knl):
+                    and bool(wino_cache.get("kn")) == routes.kn_pack):
                 ctx.wino = wino_cache["packs"]
             else:
-                ctx.wino = H.winograd_pack(weight, kn=knl)
+                ctx.wino = H.winograd_pack(weight, kn=routes.kn_pack)
                 if wino_cache is not None and wino_cache.get("want") is not None:
-                    wino_cache["packs"], wino_cache["key"], wino_cache["kn"] = ctx.wino, wino_cache["want"], knl
-        wino_f = None if (ctx.wino is None or (kn_d2 and not kn)) else ctx.wino[0]
-        keep_v = wino_f is not None and not kn and ctx.needs_input_grad[2]   # the weight gradient reuses the forward's transformed input
-        H.WINO_V[0] = None
+                    wino_cache["packs"], wino_cache["key"], wino_cache["kn"] = ctx.wino, wino_cache["want"], routes.kn_pack
+        wino_f = ctx.wino[0] if (routes.fused or routes.grouped) else None      # (not a pack built for the data-gradient alone)
+        keep_v = routes.grouped and not routes.fused and ctx.needs_input_grad[2]   # the weight gradient reuses the forward's transformed input
+        note = {}
         if stats_out is not None:
-            y, part = H.conv_forward(g, x0, x1, wp, bias, act, want_stats=True, wino=wino_f, keep_v=keep_v)
+            y, part = H.conv_forward(g, x0, x1, wp, bias, act, want_stats=True, wino=wino_f, keep_v=keep_v, routes=routes, note=note)
             stats_out.append(part)
         else:
-            if H.upfold_ok(g, 4 * x0.shape[0] * x0.shape[1] * x0.shape[2]) and x0.is_contiguous() and (x1 is None or x1.is_contiguous()):
+            if routes.upfold and x0.is_contiguous() and (x1 is None or x1.is_contiguous()):
                 # decoder Conv3x3 on [upsample(x0) | x1]: the upsample-folded route (4 taps instead of 9 on the upsampled channels)
                 # (the owning module caches the folded packs next to the plain ones for the active weight_pack_scope)
                 if fold_cache is not None and fold_cache.get("key") is not None and fold_cache.get("key") == fold_cache.get("want"):
@@ -279,10 +276,10 @@ class ConvFn(Function):
                     ctx.fold = H.upfold_pack(weight, g.C0)
                     if fold_cache is not None and fold_cache.get("want") is not None:
                         fold_cache["fold"], fold_cache["key"] = ctx.fold, fold_cache["want"]
-            y = H.conv_forward(g, x0, x1, wp, bias, act, wfold=None if ctx.fold is None else ctx.fold[0], wino=wino_f, keep_v=keep_v)
-        ctx.wino_v, H.WINO_V[0] = H.WINO_V[0], None
+            y = H.conv_forward(g, x0, x1, wp, bias, act, wfold=None if ctx.fold is None else ctx.fold[0], wino=wino_f, keep_v=keep_v,
+                               routes=routes, note=note)
+        ctx.wino_v = note["wino_v"]
         ctx.g, ctx.act = g, act
-        ctx.in_hw = (x0.shape[1] * (2 if g.up0 else 1), x0.shape[2] * (2 if g.up0 else 1))
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x0, x1, weight)
         return y
@@ -303,16 +300,18 @@ class ConvFn(Function):
             fusion("bias_grad_from_activation_pass", bool(same))
         actgrad = (x0, ctx.x0_act) if ctx.x0_act is not None else None
         dx0 = dx1 = dw = None
+        routes = H.backward_routes(g, dz.shape[0], ctx.in_hw[0], ctx.in_hw[1])      # asked once, for both gradients
         if ctx.needs_input_grad[0] or (x1 is not None and ctx.needs_input_grad[1]):
             wd = ctx.wd if ctx.wd is not None else H.pack_weight(weight, True)
             if ctx.wd_gen is not None and getattr(wd, "_segsde_gen", None) != ctx.wd_gen:
                 raise RuntimeError("the weight packs of this graph were rebuilt by a later weight_pack_scope(model): a graph "
                                    "must be consumed before the next prepack of the same weights")
             dx0 = None
+            note = {}
             box = ctx.grad_box
             if box is not None and box.get("g") is not None and x1 is None:
                 dx0, dx1 = H.conv_dgrad(g, dz, wd, weight.detach(), ctx.in_hw, accumulate_into=box["g"], actgrad=actgrad,
-                                        wino=None if ctx.wino is None else ctx.wino[1], wfpack=ctx.wp)
+                                        wino=None if ctx.wino is None else ctx.wino[1], wfpack=ctx.wp, routes=routes, note=note)
                 if dx0 is not None:
                     box["fused"] = True      # dx0 IS the residual-path gradient, now holding the sum
             if dx0 is None:
@@ -320,9 +319,10 @@ class ConvFn(Function):
                 dx0, dx1 = H.conv_dgrad(g, dz, wd, weight.detach(), ctx.in_hw, actgrad=actgrad, fold=ctx.fold,
                                         need0=ctx.needs_input_grad[0], need1=x1 is not None and ctx.needs_input_grad[1],
                                         wino=None if ctx.wino is None else ctx.wino[1],
-                                        accumulate_skip_into=None if sbox is None else sbox.get("g"), wfpack=ctx.wp)
+                                        accumulate_skip_into=None if sbox is None else sbox.get("g"), wfpack=ctx.wp, routes=routes,
+                                        note=note)
                 if sbox is not None and dx1 is not None:
-                    if H.SKIP_ACCUMULATED[0]:
+                    if note["skip_accumulated"]:
                         sbox["fused"] = True      # dx1 IS the shared tensor, now holding the sum
                     elif sbox.get("publish") and sbox.get("g") is None and dx1.is_contiguous():
                         sbox["g"] = dx1           # the next consumer's skip gradient is accumulated onto this tensor
@@ -333,13 +333,13 @@ class ConvFn(Function):
                     box["fused"] = True
             if actgrad is not None and ctx.needs_input_grad[0]:
                 # counted from what the kernel did: a shape whose epilogue cannot take the derivative ran it as a separate pass
-                fusion("activation_backward_in_dgrad_epilogue", bool(H.ACTGRAD_FUSED[0]))
+                fusion("activation_backward_in_dgrad_epilogue", bool(note["actgrad_fused"]))
             if not ctx.needs_input_grad[0]:
                 dx0 = None
             if x1 is None or not ctx.needs_input_grad[1]:
                 dx1 = None
         if ctx.needs_input_grad[2]:
-            dw = H.conv_wgrad(g, x0, x1, dz, wino_v=ctx.wino_v, out=_grad_dest(weight))
+            dw = H.conv_wgrad(g, x0, x1, dz, wino_v=ctx.wino_v, out=_grad_dest(weight), routes=routes)
             ctx.wino_v = None
         return dx0, dx1, dw, dbias, None, None, None, None, None, None, None, None, None, None
 
@@ -410,15 +410,16 @@ class BNActFn(Function):
         act, drop_p, seed, training, has_res, remask = ctx.cfg
         want_g = gamma is not None and ctx.needs_input_grad[1]
         bp = ctx.beta_param
+        note = {}
         dx, dres, dgamma, dbeta = H.bn_backward(_c(dy), y, x, mean, invstd, gamma, act, drop_p, seed, batch_stats=training,
                                                 need_dx=ctx.needs_input_grad[0],
-                                                need_dres=has_res and ctx.needs_input_grad[3], beta=beta, mask=mask,
+                                                need_dres=has_res and ctx.needs_input_grad[3], beta=beta, mask=mask, note=note,
                                                 dgamma_out=_grad_dest(gamma) if want_g else None,
                                                 dbeta_out=_grad_dest(bp) if (want_g and bp is not None and ctx.needs_input_grad[2]) else None)
         ctx.beta_param = None
         if ctx.mask_route:
             # counted from what the kernel did: shapes without a mask flavour ran this backward from the saved output
-            fusion("bn_backward_bitmask", mask is not None and bool(H.BN_MASK_USED[0]))
+            fusion("bn_backward_bitmask", mask is not None and note["mask_used"])
         if gamma is None or not ctx.needs_input_grad[1]:
             dgamma = dbeta = None
         if ctx.grad_box is not None and dres is not None:

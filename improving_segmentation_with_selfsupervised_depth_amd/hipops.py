@@ -3,10 +3,13 @@
 PyTorch is used here for device memory (``torch.empty``), the current HIP stream and dtype/shape checks only;
 every arithmetic step is a call into libsegsde_hip.so.  Activations are NHWC fp32 tensors ``[B, H, W, C]`` whose
 last dimension is contiguous (a channel slice of a wider buffer is fine: its pixel pitch ``ld`` is passed on).
+
+Which kernel family a convolution runs on is decided in one place, the route plan (forward_routes / backward_routes); by-products
+of a call (a kept Winograd transform, an epilogue fusion that was applied) come back in the ``note`` dict the caller passes.
 """
+import collections
 import ctypes
 import os
-import threading
 
 import numpy as np
 import torch
@@ -16,27 +19,6 @@ from ._lib import ConvDesc, check
 
 ACT = {"none": 0, "relu": 1, "elu": 2, "sigmoid": 3}
 
-
-class _Slot(threading.local):
-    """A one-element, per-thread side channel (``slot[0]``): conv_forward / conv_dgrad leave a route's by-product here (the
-    transformed input a Winograd forward kept, whether an epilogue fusion was applied) and the calling autograd Function
-    picks it up right after the call.  Per thread because autograd runs backward nodes on its own engine threads (one per
-    device): two devices or threads in one process must not see each other's values."""
-
-    def __init__(self, default=None):
-        self.default = default
-        self.v = default
-
-    def __getattr__(self, name):          # first touch from another thread: threading.local re-runs __init__ only with args
-        if name == "v":
-            return self.__dict__.setdefault("v", self.__dict__.get("default"))
-        raise AttributeError(name)
-
-    def __getitem__(self, i):
-        return self.v
-
-    def __setitem__(self, i, value):
-        self.v = value
 
 # Optional live kernel timing (bench.py): when set to a list, every implicit-GEMM launch -- and every launch (group) of the
 # HBM-bound kernel families, kind "hbm_*" -- is bracketed by HIP events recorded on the stream the kernel is launched on;
@@ -75,6 +57,16 @@ def _timed(kind, flops, like, launch, tag="", executed=None):
     return r
 
 
+def _taken(what, kind, flops, like, launch, tag="", executed=None, may_decline=True):
+    """one route attempt, timed: True when the launch ran, False when it declined the shape (-4: the caller goes on to its next
+    route; an error too where the caller has none, may_decline = False); any other code raises"""
+    rc = _timed(kind, flops, like, launch, tag, executed)
+    if rc == -4 and may_decline:
+        return False
+    check(rc, what)
+    return True
+
+
 # Upsample-folded route of the decoder's Conv3x3 on [upsample(x) | skip] (csrc/conv_igemm.hip, "Upsample-folded 3x3
 # convolutions"): SEGSDE_UPFOLD=0 keeps the plain 9-tap route (A/B measurements, debugging)
 UPFOLD = os.environ.get("SEGSDE_UPFOLD", "1") != "0"
@@ -82,17 +74,6 @@ UPFOLD_TAKEN = {"fwd": 0, "dgrad": 0, "wgrad": 0}    # diagnostics / tests: laun
 
 
 UPFOLD_MIN_SAVED_MACS = float(os.environ.get("SEGSDE_UPFOLD_MIN_MACS", "1e10"))
-
-
-def upfold_ok(g, pixels=None):
-    """pixels = B * H * W of the output (None: shape test only).  The folded route issues ~10 more launches per direction than
-    the plain one (pack, class launches, border launches): it is taken when the multiply-adds it saves -- 5 of 9 taps on the
-    C0 upsampled channels -- outweigh ~100 us of launches at ~130 TFLOP/s (cfg1's 2 x 256 x 512 layers stay on the plain route:
-    measured 28.9 vs 31.7 ms/step)."""
-    if not (UPFOLD and g.up0 and g.reflect and g.k == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1 and g.C0 % 32 == 0
-            and g.C1 % 32 == 0 and g.Cout % 32 == 0):
-        return False
-    return pixels is None or 5.0 * pixels * g.C0 * g.Cout >= UPFOLD_MIN_SAVED_MACS
 
 
 def upfold_pack(w_oihw, C0):
@@ -114,34 +95,6 @@ WINOGRAD = os.environ.get("SEGSDE_WINOGRAD", "1") != "0"
 WINOGRAD_MIN_CH = int(os.environ.get("SEGSDE_WINOGRAD_MIN_CH", "256"))
 WINOGRAD_MIN_MACS = float(os.environ.get("SEGSDE_WINOGRAD_MIN_MACS", "1e8"))
 WINOGRAD_TAKEN = {"fwd": 0, "dgrad": 0, "wgrad": 0}
-
-
-def winograd_ok(g, B=None, H=None, W=None, dgrad=False):
-    """Shape gate of the Winograd route.  Measured (profiles/probe_r04_winograd_gate.log, probe_r04_winograd_route.log): with the
-    transforms as separate passes the route wins from 256 channels on (1.4x at 256 channels, 1.8x at 512); at 128 channels the
-    transforms' traffic eats the 2.25x fewer multiply-adds.  The multiply-add floor keeps tiny launches (and the small-shape
-    golden tests of the direct kernels) on the direct route.  Forward: one or two sources, zero / mirrored padding (mirrored:
-    dilation 1), any dilation that divides the map into even sub-lattices.  Data-gradient: one source, zero padding."""
-    if g.compute == 1:       # (the split-bf16 mode, 2, keeps its Winograd routes: fp32 arithmetic either way)
-        return False
-    cin, cout = (g.Cout, g.C0) if dgrad else (g.Cin, g.Cout)      # the data-gradient is the convolution Cout -> C0
-    if not (WINOGRAD and g.k == 3 and g.stride == 1 and g.pad == g.dil and not g.up0 and g.cin_alg is None and g.C0 % 4 == 0
-            and cin % 32 == 0 and cout % 64 == 0 and min(g.Cin, g.Cout) >= WINOGRAD_MIN_CH and not (g.reflect and g.dil != 1)):
-        return False
-    if dgrad and (g.C1 or g.reflect):
-        return False
-    if B is None:
-        return True
-    if H % (2 * g.dil) or W % (2 * g.dil) or H < 4 * g.dil or W < 4 * g.dil:
-        return False
-    return 9.0 * B * H * W * g.Cin * g.Cout >= WINOGRAD_MIN_MACS
-
-
-def winograd_static_ok(conv):
-    """could this nn.Conv2d ever take the route (weight_pack_scope packs those up front)"""
-    return (WINOGRAD and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == conv.dilation
-            and conv.in_channels % 32 == 0 and conv.out_channels % 64 == 0
-            and min(conv.in_channels, conv.out_channels) >= WINOGRAD_MIN_CH)
 
 
 def winograd_pack(w_oihw, kn=False):
@@ -195,18 +148,16 @@ def winograd_packs_multi(weights, kn=False):
     return views
 
 
-WINO_V = _Slot(None)     # the transformed input of the last _winograd(..., keep_v=True) call (ConvFn picks it up)
-
-
-def _winograd(kind, g, x0, x1, upack, Cout, want_stats, flops, tag, bias=None, act="none", reflect=False, keep_v=False):
-    """one Winograd convolution [x0 | x1] [B,H,W,C] -> [B,H,W,Cout]; returns (y, partials or None), or None when the kernel
-    declines"""
-    B, H, W, C0 = x0.shape
-    C1 = 0 if x1 is None else x1.shape[3]
+def _winograd(kind, d, x0, x1, upack, want_stats, flops, tag, bias=None, keep_v=False):
+    """one grouped-GEMM Winograd convolution [x0 | x1] [B,H,W,C] -> [B,H,W,d.Cout] (descriptor d: ConvGeom.desc for the forward,
+    ConvGeom.dgrad_desc for the data-gradient as the convolution of dy with the flipped pack; normalised below); returns (y, partials or None, the
+    transformed input if keep_v), or None when the kernel declines"""
+    # the route's own copy: its position GEMMs run on the implicit-GEMM kernel, which reads these three fields -- always the fp32
+    # loop (compute 0: "fp32 arithmetic either way", also in the split-bf16 mode), no column split, no input divisor
+    d = ConvDesc.from_buffer_copy(d)
+    d.compute, d.nsplit, d.in_div = 0, 0, 1
+    B, H, W, Cout = d.B, d.H, d.W, d.Cout
     L = _lib.lib()
-    d = ConvDesc(B=B, H=H, W=W, C0=C0, C1=C1, ld0=nhwc_ld(x0), ld1=nhwc_ld(x1) if x1 is not None else 0, up0=0, Ho=H, Wo=W,
-                 Cout=Cout, ldy=Cout, ldy2=0, nsplit=0, KH=3, KW=3, stride=1, dil=g.dil, pad=g.dil,
-                 pad_mode=PAD_REFLECT if reflect else PAD_ZERO, in_div=1, act=ACT[act], sum2x2=0)
     nbytes = L.segsde_conv2d_winograd_workspace(ctypes.byref(d))
     if not nbytes:
         return None
@@ -216,16 +167,13 @@ def _winograd(kind, g, x0, x1, upack, Cout, want_stats, flops, tag, bias=None, a
         part = torch.empty((int(L.segsde_conv2d_winograd_stats_rows(ctypes.byref(d))), 2, Cout), dtype=torch.float64, device=x0.device)
     ws = _ws(nbytes, x0)
     Tp = (B * (H // 2) * (W // 2) + 127) // 128 * 128          # rows per position plane: whole 128-row GEMM tiles
-    vk = torch.empty((16, Tp, C0 + C1), dtype=torch.float32, device=x0.device) if keep_v else None
-    rc = _timed(kind, flops, x0, lambda: L.segsde_conv2d_winograd(ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(upack), _p(bias), _p(y),
-                                                                   _p(part), _p(vk), _p(ws), nbytes, _stream(x0)), tag + " wino",
-                executed=flops * 16.0 / 36.0)
-    if rc == -4:
+    vk = torch.empty((16, Tp, d.C0 + d.C1), dtype=torch.float32, device=x0.device) if keep_v else None
+    if not _taken("conv2d_winograd", kind, flops, x0, lambda: L.segsde_conv2d_winograd(
+            ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(upack), _p(bias), _p(y), _p(part), _p(vk), _p(ws), nbytes, _stream(x0)),
+            tag + " wino", executed=flops * 16.0 / 36.0):
         return None
-    check(rc, "conv2d_winograd")
-    WINO_V[0] = vk
     WINOGRAD_TAKEN["fwd" if kind == "conv_fwd" else "dgrad"] += 1
-    return y, part
+    return y, part, vk
 
 
 # ---- Winograd with the transforms inside the kernel (csrc/winograd_fused.hip): 3x3 / stride 1 / padding 1, one source,
@@ -250,70 +198,6 @@ WINO_FUSED_REFLECT_DGRAD_MIN_PIX = int(os.environ.get("SEGSDE_WINO_FUSED_REFLECT
 # feature's gradient collector) on the one-kernel route -- a column slice of the flipped pack -- while the upsampled source's
 # low-resolution gradient stays on the folded route's 4x4 / stride-2 launch.
 WINO_FUSED_TAKEN = {"fwd": 0, "dgrad": 0, "fwd2": 0, "dgrad_refl": 0, "dgrad_actgrad": 0, "dgrad2": 0, "wgrad": 0}
-
-
-_FUSED_SHAPE_OK = {}
-
-
-def _fused_shape_ok(B, H, W, cin, cout):
-    """segsde_winograd_fused_ok, remembered per shape (the routers ask three times per convolution call; on the launch-bound
-    small workloads a foreign-function call each time shows)"""
-    key = (B, H, W, cin, cout)
-    r = _FUSED_SHAPE_OK.get(key)
-    if r is None:
-        r = _FUSED_SHAPE_OK[key] = bool(_lib.lib().segsde_winograd_fused_ok(B, H, W, cin, cout))
-    return r
-
-
-def winograd_fused_ok(g, B=None, H=None, W=None, dgrad=False):
-    """the shapes csrc/winograd_fused.hip takes: 3x3 / stride 1 / padding 1 / dilation 1, channel counts multiples of 64.
-    One source at output resolution: up to WINO_FUSED_MAX_CH channels, zero or mirrored padding, forward and data-gradient
-    (mirrored: + segsde_reflect_adjoint_borders2).  Forward on [upsample(x0) | x1] (g.up0): C0 % 64 == 0, up to
-    WINO_FUSED2_MAX_CIN input channels, when the folded route's multiply-add share is above WINO_FUSED2_MIN_FOLD."""
-    if g.compute == 1:
-        return False
-    cin, cout = (g.Cout, g.C0) if dgrad else (g.Cin, g.Cout)
-    if not (WINOGRAD and WINO_FUSED and g.k == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1 and g.cin_alg is None
-            and cin % 64 == 0 and cout % 64 == 0):
-        return False
-    if g.up0 or g.C1:
-        # two sources without upsampling (the bottleneck-resolution layer) stay on the grouped route, which takes them
-        if dgrad or not (g.up0 and g.C0 % 64 == 0 and cin <= WINO_FUSED2_MAX_CIN and cout <= WINO_FUSED_MAX_CH
-                         and _fold_frac(g) >= WINO_FUSED2_MIN_FOLD):
-            return False
-    else:
-        if max(cin, cout) > WINO_FUSED_MAX_CH:
-            return False
-    if B is None:
-        return True
-    return _fused_shape_ok(B, H, W, cin, cout) and 9.0 * B * H * W * cin * cout >= WINOGRAD_MIN_MACS
-
-
-def winograd_fused_dgrad2_ok(g, B=None, H=None, W=None):
-    """the skip-source data-gradient of a [upsample(x0) | x1] -> Cout mirrored 3x3 convolution as the one-kernel Winograd
-    convolution Cout -> C1 (+ border kernel)"""
-    if g.compute == 1:
-        return False
-    if not (WINOGRAD and WINO_FUSED and g.k == 3 and g.stride == 1 and g.dil == 1
-            and g.pad == 1 and g.reflect and g.up0 and g.C1 and g.cin_alg is None and g.C1 % 64 == 0 and g.Cout % 64 == 0
-            and g.C0 % 64 == 0       # (the slice starts on a 64-filter block of the blocked pack layout)
-            and g.Cout <= WINO_FUSED_MAX_CH and g.Cin <= WINO_FUSED2_MAX_CIN):
-        return False
-    if B is None:
-        return True
-    return (B * H * W >= WINO_FUSED_REFLECT_DGRAD_MIN_PIX and _fused_shape_ok(B, H, W, g.Cout, g.C1)
-            and 9.0 * B * H * W * g.C1 * g.Cout >= WINOGRAD_MIN_MACS)
-
-
-def winograd_fused_static_ok(conv):
-    """could this nn.Conv2d ever take the one-kernel route (weight_pack_scope packs those in the [16][K][N] layout up front)"""
-    if not (WINOGRAD and WINO_FUSED and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0):
-        return False
-    if max(conv.in_channels, conv.out_channels) <= WINO_FUSED_MAX_CH:
-        return True
-    # the decoder's two-source layers ([upsample(x) | skip], mirrored padding)
-    return bool(getattr(conv, "reflect", False) and conv.out_channels <= WINO_FUSED_MAX_CH and conv.in_channels <= WINO_FUSED2_MAX_CIN)
 
 
 class _KnPack(torch.Tensor):
@@ -364,15 +248,13 @@ def winograd_fused(kind, x, u_kn, bias=None, act="none", want_stats=False, tag=N
     tagf = (tag or "%d+%d->%d k3 s1 d1 %dx%d" % (C0, C1, N, H, W)) + " wino-fused"
     if x1 is not None or up0:
         assert accumulate_into is None and actgrad is None and adjoint is None
-        rc = _timed(kind, flops, x, lambda: L.segsde_conv2d_winograd_fused2(
+        if not _taken("conv2d_winograd_fused2", kind, flops, x, lambda: L.segsde_conv2d_winograd_fused2(
             _p(_f32(x)), nhwc_ld(x), C0, 1 if up0 else 0, _p(x1), nhwc_ld(x1) if x1 is not None else 0, C1, B, H, W, 1 if reflect else 0,
             _p(u_kn), N, _p(bias), ACT[act], _p(y), N, _p(part), _stream(x)), tagf,
             # issued multiply-adds: 16 / 36 of the algorithmic count, 9 / 36 on the channels of a nearest-upsampled source (seven of
             # the sixteen positions are identically zero there and skipped: csrc/winograd_fused.hip, UPSKIP)
-            executed=flops * ((9.0 * C0 + 16.0 * C1) / (36.0 * (C0 + C1)) if up0 else 16.0 / 36.0))
-        if rc == -4:
+                executed=flops * ((9.0 * C0 + 16.0 * C1) / (36.0 * (C0 + C1)) if up0 else 16.0 / 36.0)):
             return None
-        check(rc, "conv2d_winograd_fused2")
         WINO_FUSED_TAKEN["fwd2"] += 1
         return y, part
     if actgrad is not None or adjoint is not None or cols is not None:
@@ -394,20 +276,16 @@ def winograd_fused(kind, x, u_kn, bias=None, act="none", want_stats=False, tag=N
                     raise RuntimeError("the mirrored-padding launches declined a shape the one-kernel data-gradient took: "
                                        "the zero-padded part is already in dx (hipops.conv_dgrad must gate this)")
             return rc
-        rc = _timed(kind, flops, x, launch, tagf, executed=flops * 16.0 / 36.0)
-        if rc == -4:
+        if not _taken("conv2d_winograd_fused_dgrad", kind, flops, x, launch, tagf, executed=flops * 16.0 / 36.0):
             return None
-        check(rc, "conv2d_winograd_fused_dgrad")
         WINO_FUSED_TAKEN["dgrad"] += 1
         WINO_FUSED_TAKEN["dgrad_refl"] += adjoint is not None
         WINO_FUSED_TAKEN["dgrad_actgrad"] += actgrad is not None
         return y, None
-    rc = _timed(kind, flops, x, lambda: L.segsde_conv2d_winograd_fused(_p(_f32(x)), nhwc_ld(x), B, H, W, C, 1 if reflect else 0, _p(u_kn), N, _p(bias),
-                                                                       ACT[act], _p(y), N, 1 if accumulate_into is not None else 0, _p(part), _stream(x)),
-                tagf, executed=flops * 16.0 / 36.0)
-    if rc == -4:
+    if not _taken("conv2d_winograd_fused", kind, flops, x, lambda: L.segsde_conv2d_winograd_fused(
+            _p(_f32(x)), nhwc_ld(x), B, H, W, C, 1 if reflect else 0, _p(u_kn), N, _p(bias), ACT[act], _p(y), N,
+            1 if accumulate_into is not None else 0, _p(part), _stream(x)), tagf, executed=flops * 16.0 / 36.0):
         return None
-    check(rc, "conv2d_winograd_fused")
     WINO_FUSED_TAKEN["fwd" if kind == "conv_fwd" else "dgrad"] += 1
     return y, part
 
@@ -431,11 +309,130 @@ WINO_FUSED_WGRAD_MAX_CIN2 = int(os.environ.get("SEGSDE_WINO_FUSED_WGRAD_MAX_CIN2
 WINO_FUSED_WGRAD_MIN_FOLD = float(os.environ.get("SEGSDE_WINO_FUSED_WGRAD_MIN_FOLD", "0.4"))
 
 
-def winograd_fused_wgrad_ok(g, B=None, H=None, W=None):
-    if g.compute == 1:       # half-precision operand mode: the direct / folded kernels (ConvGeom.compute)
+def _fold_frac(g):
+    return (4.0 * g.C0 + 9.0 * g.C1) / (9.0 * (g.C0 + g.C1))
+
+
+# ----------------------------------------------------------------------------------------------
+# Route plan: which kernel families a convolution may run on, as a function of its geometry and the [B, H, W] of its virtual input
+# (after up0).  This is the one place that holds the policy: ConvFn asks forward_routes once per forward and backward_routes once
+# per backward and hands the record to conv_forward / conv_dgrad / conv_wgrad (routes=...), which ask on their own only when
+# called without one.  What depends on tensors -- contiguity, pitches and pointer alignment, which packs the caller has, statistics
+# together with a bias or an activation, a kernel's own "declined" (-4) -- stays with those three.  The gate constants above are
+# read at call time (tests and probes assign them).
+# ----------------------------------------------------------------------------------------------
+ForwardRoutes = collections.namedtuple("ForwardRoutes", "fused grouped upfold dgrad2 kn_pack")
+BackwardRoutes = collections.namedtuple("BackwardRoutes", "dgrad_fused dgrad_grouped dgrad2 wgrad_fused wgrad_grouped wgrad_upfold")
+_NO_FORWARD_ROUTE, _NO_BACKWARD_ROUTE = ForwardRoutes(*[False] * 5), BackwardRoutes(*[False] * 6)
+
+
+def forward_routes(g, B=None, H=None, W=None, skip_grad=True):
+    """fused: the one-kernel Winograd forward, incl. its [up(x0) | x1] form; grouped: the grouped-GEMM Winograd forward; upfold: the
+    upsample-folded direct forward; dgrad2: the skip-source data-gradient will want the flipped [16][K][N] pack (a backward gate: not
+    asked with skip_grad = False); kn_pack: the transformed packs to build are [16][K][N] ones.  B = None: shape-free answers."""
+    if g.k != 3 or g.stride != 1:
+        return _NO_FORWARD_ROUTE
+    # the Winograd routes are fp32 kernels: not taken in the half-precision operand mode (ConvGeom.compute 1; the split-bf16 mode, 2,
+    # keeps them: fp32 arithmetic either way), nor with the zero pad channels of a stem
+    wino = bool(WINOGRAD) and g.compute != 1 and g.cin_alg is None
+    fused = wino and _fused_route(g, False, B, H, W)
+    dgrad2 = wino and skip_grad and _dgrad2_route(g, B, H, W)
+    return ForwardRoutes(fused, wino and _grouped_route(g, False, B, H, W), _upfold_route(g, None if B is None else B * H * W), dgrad2,
+                         fused or dgrad2)
+
+
+def backward_routes(g, B=None, H=None, W=None):
+    """The routes of the data-gradient (one-kernel, grouped, one-kernel for the skip source of a two-source layer whose upsampled
+    source stays on the folded route) and of the weight gradient (one-kernel, grouped, upsample-folded), tried in that order"""
+    if g.k != 3 or g.stride != 1:
+        return _NO_BACKWARD_ROUTE
+    upfold = _upfold_route(g, None if B is None else B * H * W)
+    if not WINOGRAD or g.compute == 1 or g.cin_alg is not None:          # (as in forward_routes)
+        return BackwardRoutes(False, False, False, False, False, upfold)
+    return BackwardRoutes(_fused_route(g, True, B, H, W), _grouped_route(g, True, B, H, W), _dgrad2_route(g, B, H, W),
+                          _wgrad_fused_route(g, B, H, W), _grouped_route(g, False, B, H, W), upfold)
+
+
+def _upfold_route(g, pixels):
+    """pixels = B * H * W of the output (None: shape test only).  The folded route issues ~10 more launches per direction than
+    the plain one (pack, class launches, border launches): it is taken when the multiply-adds it saves -- 5 of 9 taps on the
+    C0 upsampled channels -- outweigh ~100 us of launches at ~130 TFLOP/s (cfg1's 2 x 256 x 512 layers stay on the plain route:
+    measured 28.9 vs 31.7 ms/step)."""
+    if not (UPFOLD and g.up0 and g.reflect and g.dil == 1 and g.pad == 1 and g.C0 % 32 == 0 and g.C1 % 32 == 0 and g.Cout % 32 == 0):
         return False
-    if not (WINOGRAD and WINO_FUSED and WINO_FUSED_WGRAD and g.k == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1
-            and g.cin_alg is None and g.C0 % 32 == 0 and g.C1 % 32 == 0 and g.Cout % 64 == 0 and g.Cout <= WINO_FUSED_WGRAD_MAX_CH):
+    return pixels is None or 5.0 * pixels * g.C0 * g.Cout >= UPFOLD_MIN_SAVED_MACS
+
+
+def _grouped_route(g, dgrad, B, H, W):
+    """Shape gate of the grouped-GEMM Winograd route.  Measured (profiles/probe_r04_winograd_gate.log, probe_r04_winograd_route.log):
+    with the transforms as separate passes the route wins from 256 channels on (1.4x at 256 channels, 1.8x at 512); at 128 channels
+    the transforms' traffic eats the 2.25x fewer multiply-adds.  The multiply-add floor keeps tiny launches (and the small-shape
+    golden tests of the direct kernels) on the direct route.  Forward and weight gradient: one or two sources, zero / mirrored
+    padding (mirrored: dilation 1), any dilation that divides the map into even sub-lattices.  Data-gradient: one source, zero
+    padding."""
+    cin, cout = (g.Cout, g.C0) if dgrad else (g.Cin, g.Cout)      # the data-gradient is the convolution Cout -> C0
+    if not (g.pad == g.dil and not g.up0 and g.C0 % 4 == 0 and cin % 32 == 0 and cout % 64 == 0
+            and min(g.Cin, g.Cout) >= WINOGRAD_MIN_CH and not (g.reflect and g.dil != 1)):
+        return False
+    if dgrad and (g.C1 or g.reflect):
+        return False
+    if B is None:
+        return True
+    if H % (2 * g.dil) or W % (2 * g.dil) or H < 4 * g.dil or W < 4 * g.dil:
+        return False
+    return 9.0 * B * H * W * g.Cin * g.Cout >= WINOGRAD_MIN_MACS
+
+
+_FUSED_SHAPE_OK = {}
+
+
+def _fused_shape_ok(B, H, W, cin, cout):
+    """segsde_winograd_fused_ok, remembered per shape (a foreign-function call per convolution and direction shows on the
+    launch-bound small workloads)"""
+    key = (B, H, W, cin, cout)
+    r = _FUSED_SHAPE_OK.get(key)
+    if r is None:
+        r = _FUSED_SHAPE_OK[key] = bool(_lib.lib().segsde_winograd_fused_ok(B, H, W, cin, cout))
+    return r
+
+
+def _fused_route(g, dgrad, B, H, W):
+    """the shapes csrc/winograd_fused.hip takes: 3x3 / stride 1 / padding 1 / dilation 1, channel counts multiples of 64.
+    One source at output resolution: up to WINO_FUSED_MAX_CH channels, zero or mirrored padding, forward and data-gradient
+    (mirrored: + segsde_reflect_adjoint_borders2).  Forward on [upsample(x0) | x1] (g.up0): C0 % 64 == 0, up to
+    WINO_FUSED2_MAX_CIN input channels, when the folded route's multiply-add share is above WINO_FUSED2_MIN_FOLD."""
+    cin, cout = (g.Cout, g.C0) if dgrad else (g.Cin, g.Cout)
+    if not (WINO_FUSED and g.dil == 1 and g.pad == 1 and cin % 64 == 0 and cout % 64 == 0):
+        return False
+    if g.up0 or g.C1:
+        # two sources without upsampling (the bottleneck-resolution layer) stay on the grouped route, which takes them
+        if dgrad or not (g.up0 and g.C0 % 64 == 0 and cin <= WINO_FUSED2_MAX_CIN and cout <= WINO_FUSED_MAX_CH
+                         and _fold_frac(g) >= WINO_FUSED2_MIN_FOLD):
+            return False
+    elif max(cin, cout) > WINO_FUSED_MAX_CH:
+        return False
+    if B is None:
+        return True
+    return _fused_shape_ok(B, H, W, cin, cout) and 9.0 * B * H * W * cin * cout >= WINOGRAD_MIN_MACS
+
+
+def _dgrad2_route(g, B, H, W):
+    """the skip-source data-gradient of a [upsample(x0) | x1] -> Cout mirrored 3x3 convolution as the one-kernel Winograd
+    convolution Cout -> C1 (+ border kernel)"""
+    if not (WINO_FUSED and g.dil == 1 and g.pad == 1 and g.reflect and g.up0 and g.C1 and g.C1 % 64 == 0 and g.Cout % 64 == 0
+            and g.C0 % 64 == 0       # (the slice starts on a 64-filter block of the blocked pack layout)
+            and g.Cout <= WINO_FUSED_MAX_CH and g.Cin <= WINO_FUSED2_MAX_CIN):
+        return False
+    if B is None:
+        return True
+    return (B * H * W >= WINO_FUSED_REFLECT_DGRAD_MIN_PIX and _fused_shape_ok(B, H, W, g.Cout, g.C1)
+            and 9.0 * B * H * W * g.C1 * g.Cout >= WINOGRAD_MIN_MACS)
+
+
+def _wgrad_fused_route(g, B, H, W):
+    """the weight gradient on the one-kernel scheme (csrc/winograd_wgrad.hip)"""
+    if not (WINO_FUSED and WINO_FUSED_WGRAD and g.dil == 1 and g.pad == 1 and g.C0 % 32 == 0 and g.C1 % 32 == 0 and g.Cout % 64 == 0
+            and g.Cout <= WINO_FUSED_WGRAD_MAX_CH):
         return False
     if g.up0 or g.C1:
         if not (g.up0 and g.Cin <= WINO_FUSED_WGRAD_MAX_CIN2 and _fold_frac(g) >= WINO_FUSED_WGRAD_MIN_FOLD):
@@ -447,8 +444,50 @@ def winograd_fused_wgrad_ok(g, B=None, H=None, W=None):
     return H % 2 == 0 and W % 2 == 0 and H >= 4 and W >= 4 and 9.0 * B * H * W * g.Cin * g.Cout >= WINOGRAD_MIN_MACS
 
 
-def _fold_frac(g):
-    return (4.0 * g.C0 + 9.0 * g.C1) / (9.0 * (g.C0 + g.C1))
+# the gates by name: views of the plan (tests, tools and probes ask these; the package itself asks the plan)
+def winograd_ok(g, B=None, H=None, W=None, dgrad=False):
+    return backward_routes(g, B, H, W).dgrad_grouped if dgrad else forward_routes(g, B, H, W).grouped
+
+
+def winograd_fused_ok(g, B=None, H=None, W=None, dgrad=False):
+    return backward_routes(g, B, H, W).dgrad_fused if dgrad else forward_routes(g, B, H, W).fused
+
+
+def winograd_fused_dgrad2_ok(g, B=None, H=None, W=None):
+    return backward_routes(g, B, H, W).dgrad2
+
+
+def winograd_fused_wgrad_ok(g, B=None, H=None, W=None):
+    return backward_routes(g, B, H, W).wgrad_fused
+
+
+def upfold_ok(g, pixels=None):
+    """(asked by pixel count, B * H * W of the output, where the plans take a map: their own helper)"""
+    return g.k == 3 and g.stride == 1 and _upfold_route(g, pixels)
+
+
+# the shape-free questions weight_pack_scope asks of an nn.Conv2d before any input is seen
+def winograd_static_ok(conv):
+    """could this nn.Conv2d ever take the grouped route"""
+    return (WINOGRAD and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == conv.dilation
+            and conv.in_channels % 32 == 0 and conv.out_channels % 64 == 0
+            and min(conv.in_channels, conv.out_channels) >= WINOGRAD_MIN_CH)
+
+
+def winograd_fused_static_ok(conv):
+    """could this nn.Conv2d ever take the one-kernel route"""
+    if not (WINOGRAD and WINO_FUSED and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0):
+        return False
+    if max(conv.in_channels, conv.out_channels) <= WINO_FUSED_MAX_CH:
+        return True
+    # the decoder's two-source layers ([upsample(x) | skip], mirrored padding)
+    return bool(getattr(conv, "reflect", False) and conv.out_channels <= WINO_FUSED_MAX_CH and conv.in_channels <= WINO_FUSED2_MAX_CIN)
+
+
+def winograd_prepack_layout(conv):
+    """the transformed packs weight_pack_scope(model) builds up front: True the one-kernel route's layout, False the grouped, None no pack"""
+    return True if winograd_fused_static_ok(conv) else (False if winograd_static_ok(conv) else None)
 
 
 def _live_tap_frac(g, H, W, wgrad=False):
@@ -559,6 +598,8 @@ class ConvGeom:
         """cin_alg: input channels of the convolution as the REFERENCE defines it when the launch carries zero pad channels
         (network stems: 3 -> 4, 6 -> 8): the algorithmic FLOP count of the bench uses it, the executed count the padded width"""
         self.C0, self.C1, self.Cout, self.k = int(C0), int(C1), int(Cout), int(k)
+        self.Cin = self.C0 + self.C1       # (a plain attribute, not a property: the route plan reads it ~10 times per call, and
+        #                                    C0 / C1 are fixed at construction -- nothing reassigns them)
         self.cin_alg = int(cin_alg) if cin_alg else None
         self.stride, self.dil, self.pad, self.reflect, self.up0 = int(stride), int(dil), int(pad), bool(reflect), bool(up0)
         # segsde_conv_desc.compute of every launch of this convolution (forward, data-gradient, weight gradient): 1 under the
@@ -570,16 +611,32 @@ class ConvGeom:
             raise NotImplementedError("reflection padding is implemented for the reference's 3x3/s1/p1 Conv3x3 only")
 
     @property
-    def Cin(self):
-        return self.C0 + self.C1
-
-    @property
     def CinAlg(self):
         return self.cin_alg if self.cin_alg else self.C0 + self.C1
 
     def out_hw(self, H, W):
         e = self.dil * (self.k - 1) + 1
         return (H + 2 * self.pad - e) // self.stride + 1, (W + 2 * self.pad - e) // self.stride + 1
+
+    def desc(self, B, H, W, Ho=None, Wo=None, ld0=None, ld1=None, act=0):
+        """the launch descriptor as the forward sees the convolution (forward, weight gradient, every upsample-folded entry) on a
+        [B, H, W] virtual input; Ho, Wo: of the output (default out_hw), ld0 / ld1: the sources' pixel pitches (default dense)"""
+        if Ho is None:
+            Ho, Wo = self.out_hw(H, W)
+        return ConvDesc(B=B, H=H, W=W, C0=self.C0, C1=self.C1, ld0=self.C0 if ld0 is None else ld0, ld1=self.C1 if ld1 is None else ld1,
+                        up0=int(self.up0), Ho=Ho, Wo=Wo, Cout=self.Cout, ldy=self.Cout, ldy2=0, nsplit=0, KH=self.k, KW=self.k,
+                        stride=self.stride, dil=self.dil, pad=self.pad, pad_mode=PAD_REFLECT if self.reflect else PAD_ZERO, in_div=1,
+                        act=act, sum2x2=0, compute=self.compute)
+
+    def dgrad_desc(self, B, H, W, Ho=None, Wo=None, ld0=None, sum2x2=0, accumulate=0):
+        """the data-gradient's: the stride-1 convolution of dy [B,Ho,Wo,Cout] (pitch ld0) with the flipped pack, output columns split
+        into dx0 | dx1; sum2x2: the upsample adjoint's 2x2 sum in the epilogue, accumulate: the result is added onto dx0"""
+        if Ho is None:
+            Ho, Wo = self.out_hw(H, W)
+        return ConvDesc(B=B, H=Ho, W=Wo, C0=self.Cout, C1=0, ld0=self.Cout if ld0 is None else ld0, ld1=0, up0=0, Ho=H, Wo=W,
+                        Cout=self.Cin, ldy=self.C0, ldy2=self.C1, nsplit=self.C0, KH=self.k, KW=self.k, stride=1, dil=self.dil,
+                        pad=(self.k - 1) * self.dil - self.pad, pad_mode=PAD_REFLECT_ADJOINT if self.reflect else PAD_ZERO,
+                        in_div=self.stride, act=0, sum2x2=sum2x2, accumulate=accumulate, compute=self.compute)
 
 
 def pack_weight(w_oihw, for_dgrad=False):
@@ -640,13 +697,16 @@ def pack_weights_multi(weights):
     return views
 
 
-def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=None, wino=None, keep_v=False, residual=None):
+def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=None, wino=None, keep_v=False, residual=None,
+                 routes=None, note=None):
     """y = act(conv(cat[up?(x0), x1]) + bias).  x0: [B,H0,W0,C0] (H0 = H/2 if g.up0), x1: [B,H,W,C1] or None.
     want_stats: also return the per-tile statistics partials of y for the BatchNorm that follows ([rows,2,Cout] doubles,
     or None when this shape cannot fuse them) -> (y, partials).
     residual: [B,Ho,Wo,Cout] added before the activation, y = act((conv + bias) + residual), on the direct route only
     (segsde_conv2d_forward_residual; no statistics, no Winograd / folded route) -> y, or None when the launch declines the shape
-    (the caller then runs the unfused sequence)."""
+    (the caller then runs the unfused sequence).
+    routes: forward_routes(g, B, H, W), if the caller has asked already.  note: a dict that receives "wino_v": the transformed input
+    a grouped Winograd launch kept for the weight gradient (keep_v), None on every other route."""
     B, H0, W0, C0 = x0.shape
     H, W = (2 * H0, 2 * W0) if g.up0 else (H0, W0)
     assert C0 == g.C0 and (g.C1 == 0) == (x1 is None)
@@ -654,64 +714,55 @@ def conv_forward(g, x0, x1, wpack, bias, act="none", want_stats=False, wfold=Non
         assert tuple(x1.shape) == (B, H, W, g.C1), (tuple(x1.shape), (B, H, W, g.C1))
     Ho, Wo = g.out_hw(H, W)
     y = torch.empty((B, Ho, Wo, g.Cout), dtype=torch.float32, device=x0.device)
-    d = ConvDesc(B=B, H=H, W=W, C0=g.C0, C1=g.C1, ld0=nhwc_ld(x0), ld1=nhwc_ld(x1) if x1 is not None else 0,
-                 up0=int(g.up0), Ho=Ho, Wo=Wo, Cout=g.Cout, ldy=g.Cout, ldy2=0, nsplit=0, KH=g.k, KW=g.k,
-                 stride=g.stride, dil=g.dil, pad=g.pad, pad_mode=PAD_REFLECT if g.reflect else PAD_ZERO, in_div=1,
-                 act=ACT[act], sum2x2=0, compute=g.compute)
+    d = g.desc(B, H, W, Ho, Wo, nhwc_ld(x0), nhwc_ld(x1) if x1 is not None else 0, ACT[act])
+    L = _lib.lib()
     flops = 2.0 * B * Ho * Wo * g.Cout * g.CinAlg * g.k * g.k
     flops_x = flops * g.Cin / g.CinAlg * _live_tap_frac(g, H, W)   # executed: zero pad channels of a stem are multiplied too, dead tap rows are not
+    if note is not None:
+        note["wino_v"] = None
     if residual is not None:
         assert not want_stats and wfold is None and wino is None and tuple(residual.shape) == tuple(y.shape)
-        rc = _timed("conv_fwd", flops, x0, lambda: _lib.lib().segsde_conv2d_forward_residual(
-            ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(bias), _p(_f32(residual)), nhwc_ld(residual), _p(y), _stream(x0)),
-            _tag(g, H, W) + " res", executed=flops_x)
-        if rc == -4:
+        if not _taken("conv2d_forward_residual", "conv_fwd", flops, x0, lambda: L.segsde_conv2d_forward_residual(
+                ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(bias), _p(_f32(residual)), nhwc_ld(residual), _p(y), _stream(x0)),
+                _tag(g, H, W) + " res", executed=flops_x):
             return None
-        check(rc, "conv2d_forward_residual")
         _note_compute(d, 0, "fwd")
         return y
-    if isinstance(wino, _KnPack):
-        if (not want_stats or (bias is None and act == "none")) and winograd_fused_ok(g, B, H, W):
-            r = winograd_fused("conv_fwd", x0, wino, bias=bias, act=act, want_stats=want_stats, tag=_tag(g, H, W), reflect=g.reflect,
-                               x1=x1, up0=g.up0)
-            if r is not None:
-                return r if want_stats else r[0]
-    elif wino is not None and not g.up0 and (not want_stats or (bias is None and act == "none")) and winograd_ok(g, B, H, W):
-        WINO_V[0] = None
-        r = _winograd("conv_fwd", g, x0, x1, wino, g.Cout, want_stats, flops, _tag(g, H, W), bias=bias, act=act, reflect=g.reflect,
-                      keep_v=keep_v)
+    if wino is not None and (not want_stats or (bias is None and act == "none")):
+        if routes is None:
+            routes = forward_routes(g, B, H, W, skip_grad=False)
+        r = None
+        if isinstance(wino, _KnPack):
+            if routes.fused:
+                r = winograd_fused("conv_fwd", x0, wino, bias=bias, act=act, want_stats=want_stats, tag=_tag(g, H, W), reflect=g.reflect,
+                                   x1=x1, up0=g.up0)
+        elif routes.grouped:
+            r = _winograd("conv_fwd", d, x0, x1, wino, want_stats, flops, _tag(g, H, W), bias=bias, keep_v=keep_v)
+            if r is not None and note is not None:
+                note["wino_v"] = r[2]
         if r is not None:
-            return r if want_stats else r[0]
+            return r[:2] if want_stats else r[0]
     if wfold is not None and not want_stats:
-        rc = _timed("conv_fwd", flops, x0, lambda: _lib.lib().segsde_conv2d_forward_upfold(
-            ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(wfold), _p(bias), _p(y), _stream(x0)), _tag(g, H, W) + " fold",
-            executed=flops * _fold_frac(g))
-        if rc == 0:
+        if _taken("conv2d_forward_upfold", "conv_fwd", flops, x0, lambda: L.segsde_conv2d_forward_upfold(
+                ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(wfold), _p(bias), _p(y), _stream(x0)), _tag(g, H, W) + " fold",
+                executed=flops * _fold_frac(g)):
             UPFOLD_TAKEN["fwd"] += 1
             _note_compute(d, 4, "fwd")
             return y
-        if rc != -4:
-            check(rc, "conv2d_forward_upfold")
     part = None
     if want_stats and bias is None and act == "none":
-        rows = int(_lib.lib().segsde_conv2d_stats_rows(ctypes.byref(d)))
+        rows = int(L.segsde_conv2d_stats_rows(ctypes.byref(d)))
         if rows > 0:
             part = torch.empty((rows, 2, g.Cout), dtype=torch.float64, device=x0.device)
-    _timed("conv_fwd", flops, x0, lambda: check(_lib.lib().segsde_conv2d_forward_stats(
+    _timed("conv_fwd", flops, x0, lambda: check(L.segsde_conv2d_forward_stats(
         ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(wpack), _p(bias), _p(y), None, _p(part), _stream(x0)), "conv2d_forward"),
         _tag(g, H, W), executed=flops_x)
     _note_compute(d, 0, "fwd")
     return (y, part) if want_stats else y
 
 
-ACTGRAD_FUSED = _Slot(False)      # did the last conv_dgrad(actgrad=...) apply the derivative in its epilogue (functional.py counts from this)
-
-
-SKIP_ACCUMULATED = _Slot(False)   # did the last conv_dgrad(accumulate_skip_into=...) add its skip gradient onto that tensor
-
-
 def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_into=None, actgrad=None, fold=None, wino=None,
-               accumulate_skip_into=None, wfpack=None):
+               accumulate_skip_into=None, wfpack=None, routes=None, note=None):
     """Data gradient(s) of conv_forward w.r.t. (x0, x1).  dy: [B,Ho,Wo,Cout]; in_hw = (H, W) of the virtual input.
     wfpack: the FORWARD pack, if the caller has it (the mirrored-padding border kernel of the one-kernel Winograd route reads it;
     without it a mirrored convolution's data-gradient runs on the direct reflection-adjoint kernel).
@@ -721,12 +772,16 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
     when this shape cannot accumulate in place -- the caller then adds).
     actgrad = (x0_saved, kind): x0 is the OUTPUT of an activation ("relu" / "elu" / "sigmoid"); dx0 is returned already
     multiplied by its derivative, i.e. as the gradient w.r.t. the PRE-activation (fused into the kernel epilogue where the
-    shape allows, otherwise by a separate pass)."""
+    shape allows, otherwise by a separate pass).
+    routes: backward_routes(g, B, H, W), if the caller has asked already.  note: a dict that receives "actgrad_fused" (actgrad's
+    derivative was applied in a kernel epilogue) and "skip_accumulated" (dx1 is accumulate_skip_into, holding the sum), else False."""
     B, Ho, Wo, Cout = dy.shape
     H, W = in_hw
     assert Cout == g.Cout
-    ACTGRAD_FUSED[0] = False
-    SKIP_ACCUMULATED[0] = False
+    note = {} if note is None else note
+    note["actgrad_fused"] = note["skip_accumulated"] = False
+    if routes is None and wino is not None:
+        routes = backward_routes(g, B, H, W)
     dx1 = torch.empty((B, H, W, g.C1), dtype=torch.float32, device=dy.device) if g.C1 else None
     L = _lib.lib()
     flops = 2.0 * B * Ho * Wo * Cout * g.CinAlg * g.k * g.k
@@ -735,29 +790,25 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         ag_y, ag_kind = actgrad[0], ACT[actgrad[1]]
         ag_ld = nhwc_ld(ag_y)
 
+    def desc(sum2x2=0, accumulate=0):
+        return g.dgrad_desc(B, H, W, Ho, Wo, nhwc_ld(dy), sum2x2, accumulate)
+
     if isinstance(wino, _KnPack):
         # (a mirrored convolution: the border kernel reads the FORWARD pack; without one the direct reflection-adjoint kernel below)
-        if (winograd_fused_ok(g, B, H, W, dgrad=True) and (Ho, Wo) == (H, W)
+        if (routes.dgrad_fused and (Ho, Wo) == (H, W)
                 and (not g.reflect or (wfpack is not None and B * H * W >= WINO_FUSED_REFLECT_DGRAD_MIN_PIX
                                        and _reflect_borders2_ok(dy, H, W, g.C0, Cout)))
                 and (actgrad is None or (ag_ld % 4 == 0 and ag_y.data_ptr() % 16 == 0))):
             r = winograd_fused("conv_dgrad", dy, wino, tag=_tag(g, H, W), accumulate_into=accumulate_into, actgrad=actgrad,
                                adjoint=wfpack if g.reflect else None)
             if r is not None:
-                ACTGRAD_FUSED[0] = actgrad is not None
+                note["actgrad_fused"] = actgrad is not None
                 return r[0], None
-    elif (wino is not None and accumulate_into is None and actgrad is None and not g.reflect and g.C1 == 0
-            and winograd_ok(g, B, H, W, dgrad=True) and (Ho, Wo) == (H, W)):
-        # zero-padded 3x3 / stride 1: dX is the same convolution of dY with the flipped, transposed kernel
-        r = _winograd("conv_dgrad", g, dy, None, wino, g.C0, False, flops, _tag(g, H, W))
+    elif wino is not None and accumulate_into is None and actgrad is None and routes.dgrad_grouped and (Ho, Wo) == (H, W):
+        # zero-padded 3x3 / stride 1, one source: dX is the same convolution of dY with the flipped, transposed kernel
+        r = _winograd("conv_dgrad", desc(), dy, None, wino, False, flops, _tag(g, H, W))
         if r is not None:
             return r[0], None
-
-    def desc(sum2x2, accumulate=0):
-        return ConvDesc(B=B, H=Ho, W=Wo, C0=Cout, C1=0, ld0=nhwc_ld(dy), ld1=0, up0=0, Ho=H, Wo=W, Cout=g.Cin, ldy=g.C0,
-                        ldy2=g.C1, nsplit=g.C0, KH=g.k, KW=g.k, stride=1, dil=g.dil, pad=(g.k - 1) * g.dil - g.pad,
-                        pad_mode=PAD_REFLECT_ADJOINT if g.reflect else PAD_ZERO, in_div=g.stride, act=0, sum2x2=sum2x2,
-                        accumulate=accumulate, compute=g.compute)
 
     def launch(d, y, y2, fuse):
         return L.segsde_conv2d_dgrad_actgrad(ctypes.byref(d), _p(_f32(dy)), None, _p(wdpack), None, _p(y), _p(y2), None,
@@ -776,13 +827,11 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         if g.up0 or g.C1 or tuple(acc.shape) != (B, H, W, g.C0) or not acc.is_contiguous():
             return None, None
         d = desc(0, 1)
-        rc = _timed("conv_dgrad", flops, dy, lambda: launch(d, acc, None, actgrad is not None), _tag(g, H, W),
-                    executed=flops * _live_tap_frac(g, H, W))
-        if rc == -4:
+        if not _taken("conv2d dgrad (accumulate)", "conv_dgrad", flops, dy, lambda: launch(d, acc, None, actgrad is not None),
+                      _tag(g, H, W), executed=flops * _live_tap_frac(g, H, W)):
             return None, None
-        check(rc, "conv2d dgrad (accumulate)")
         _note_compute(d, 1, "dgrad")
-        ACTGRAD_FUSED[0] = actgrad is not None
+        note["actgrad_fused"] = actgrad is not None
         return acc, None
     if g.up0 and fold is not None and accumulate_into is None:
         # upsample-folded route: low-resolution gradient as a 4x4 stride-2 convolution of dy (+ clamp adjoint on the border),
@@ -803,8 +852,7 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         # round 5: the skip-source gradient on the one-kernel Winograd route (flipped pack's columns [C0, C0 + C1), border kernel on
         # the forward pack's same channels); the folded call below then computes the upsampled source's gradient only
         w1 = None
-        if (dx1f is not None and isinstance(wino, _KnPack) and wfpack is not None and winograd_fused_dgrad2_ok(g, B, H, W)
-                and (Ho, Wo) == (H, W)):
+        if dx1f is not None and isinstance(wino, _KnPack) and wfpack is not None and routes.dgrad2 and (Ho, Wo) == (H, W):
             r = winograd_fused("conv_dgrad", dy, wino, tag="%d+0->%d k3 s1 d1 %dx%d refl skip-of-%d+%d" % (Cout, g.C1, H, W, g.C0, g.C1),
                                accumulate_into=acc1, adjoint=wfpack, cols=(g.C0, g.C1))
             if r is not None:
@@ -812,52 +860,48 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
                 WINO_FUSED_TAKEN["dgrad2"] += 1
         if w1 is not None:
             if dx0 is None:
-                SKIP_ACCUMULATED[0] = acc1 is not None
+                note["skip_accumulated"] = acc1 is not None
                 return None, w1
             dx1f = None
-        df = ConvDesc(B=B, H=H, W=W, C0=g.C0, C1=g.C1, ld0=g.C0, ld1=g.C1, up0=1, Ho=Ho, Wo=Wo, Cout=Cout, ldy=Cout, ldy2=0,
-                      nsplit=0, KH=3, KW=3, stride=1, dil=1, pad=1, pad_mode=PAD_REFLECT, in_div=1, act=0, sum2x2=0, compute=g.compute)
+        df = g.desc(B, H, W, Ho, Wo)
         fr = ((4.0 * g.C0 if dx0 is not None else 0.0) + (9.0 * g.C1 if dx1f is not None else 0.0)) / (9.0 * g.Cin)
         if w1 is not None:
             flops = flops * g.C0 / g.Cin          # the skip channels' multiply-adds were counted (and timed) with the Winograd launch
             fr = 4.0 / 9.0
-        rc = _timed("conv_dgrad", flops, dy, lambda: L.segsde_conv2d_dgrad_upfold(
-            ctypes.byref(df), _p(_f32(dy)), nhwc_ld(dy), _p(wdpack), _p(wfold), _p(wdfold), _p(dx0), _p(dx1f), 1 if acc1 is not None else 0,
-            _p(ag_y) if dx0 is not None else None, ag_ld, ag_kind, _stream(dy)), _tag(g, H, W) + " fold", executed=flops * fr)
-        if rc == 0:
+        # (with the skip gradient already in place the folded launch has to take the upsampled source: no decline then)
+        if _taken("conv2d_dgrad_upfold" + (" (upsampled source only)" if w1 is not None else ""), "conv_dgrad", flops, dy,
+                  lambda: L.segsde_conv2d_dgrad_upfold(
+                      ctypes.byref(df), _p(_f32(dy)), nhwc_ld(dy), _p(wdpack), _p(wfold), _p(wdfold), _p(dx0), _p(dx1f),
+                      1 if acc1 is not None else 0, _p(ag_y) if dx0 is not None else None, ag_ld, ag_kind, _stream(dy)),
+                  _tag(g, H, W) + " fold", executed=flops * fr, may_decline=w1 is None):
             UPFOLD_TAKEN["dgrad"] += 1
             _note_compute(df, 5, "dgrad")
-            SKIP_ACCUMULATED[0] = acc1 is not None
-            ACTGRAD_FUSED[0] = actgrad is not None and dx0 is not None
+            note["skip_accumulated"] = acc1 is not None
+            note["actgrad_fused"] = actgrad is not None and dx0 is not None
             return dx0, (w1 if w1 is not None else dx1f)
-        if w1 is not None:
-            check(rc, "conv2d_dgrad_upfold (upsampled source only)")
-        if rc != -4:
-            check(rc, "conv2d_dgrad_upfold")
     if g.up0:
         # fused: the 2x2 sum of the upsample adjoint happens in the GEMM epilogue (no full-resolution gradient tensor)
         dx0 = torch.empty((B, H // 2, W // 2, g.C0), dtype=torch.float32, device=dy.device)
         d = desc(1)
-        rc = _timed("conv_dgrad", flops, dy, lambda: launch(d, dx0, dx1, actgrad is not None), _tag(g, H, W))
-        if rc == 0:
-            ACTGRAD_FUSED[0] = actgrad is not None
+        if _taken("conv2d dgrad (fused upsample adjoint)", "conv_dgrad", flops, dy, lambda: launch(d, dx0, dx1, actgrad is not None),
+                  _tag(g, H, W)):
+            note["actgrad_fused"] = actgrad is not None
             _note_compute(d, 1, "dgrad")
             return dx0, dx1
-        if rc == -4 and actgrad is not None:
+        if actgrad is not None:          # declined with the derivative in its epilogue: once more without (not timed again)
             rc = launch(d, dx0, dx1, False)
             if rc == 0:
                 _note_compute(d, 1, "dgrad")
                 return finish_unfused(dx0), dx1
-        if rc != -4:
-            check(rc, "conv2d dgrad (fused upsample adjoint)")
+            if rc != -4:
+                check(rc, "conv2d dgrad (fused upsample adjoint)")
     full0 = torch.empty((B, H, W, g.C0), dtype=torch.float32, device=dy.device)
     d = desc(0)
     fused = actgrad is not None and not g.up0
-    rc = _timed("conv_dgrad", flops, dy, lambda: launch(d, full0, dx1, fused), _tag(g, H, W), executed=flops * _live_tap_frac(g, H, W))
-    if rc == -4 and fused:
-        fused = False
-        rc = launch(d, full0, dx1, False)
-    check(rc, "conv2d dgrad")
+    if not _taken("conv2d dgrad", "conv_dgrad", flops, dy, lambda: launch(d, full0, dx1, fused), _tag(g, H, W),
+                  executed=flops * _live_tap_frac(g, H, W), may_decline=fused):
+        fused = False                    # (as above)
+        check(launch(d, full0, dx1, False), "conv2d dgrad")
     _note_compute(d, 1, "dgrad")
     if g.up0:
         dx0 = torch.empty((B, H // 2, W // 2, g.C0), dtype=torch.float32, device=dy.device)
@@ -865,19 +909,21 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
               "upsample2x_backward")
     else:
         dx0 = full0
-    ACTGRAD_FUSED[0] = fused
+    note["actgrad_fused"] = fused
     return (dx0 if fused else finish_unfused(dx0)), dx1
 
 
-def conv_wgrad(g, x0, x1, dy, wino_v=None, out=None):
-    """dW in OIHW layout.  wino_v: the transformed input the forward's Winograd call kept (hipops.WINO_V), if any.
-    out: a dense [Cout, Cin, k, k] tensor to write into (the parameter's slice of a gradient bucket, ddp.grad_destination)."""
+def conv_wgrad(g, x0, x1, dy, wino_v=None, out=None, routes=None):
+    """dW in OIHW layout.  wino_v: the transformed input the forward's grouped Winograd launch kept (conv_forward's note["wino_v"]),
+    if any.  out: a dense [Cout, Cin, k, k] tensor to write into (the parameter's slice of a gradient bucket, ddp.grad_destination).
+    routes: backward_routes(g, B, H, W), if the caller has asked already."""
     B, H0, W0, _ = x0.shape
     H, W = (2 * H0, 2 * W0) if g.up0 else (H0, W0)
     _, Ho, Wo, Cout = dy.shape
-    d = ConvDesc(B=B, H=H, W=W, C0=g.C0, C1=g.C1, ld0=nhwc_ld(x0), ld1=nhwc_ld(x1) if x1 is not None else 0,
-                 up0=int(g.up0), Ho=Ho, Wo=Wo, Cout=Cout, ldy=Cout, ldy2=0, nsplit=0, KH=g.k, KW=g.k, stride=g.stride,
-                 dil=g.dil, pad=g.pad, pad_mode=PAD_REFLECT if g.reflect else PAD_ZERO, in_div=1, act=0, sum2x2=0, compute=g.compute)
+    assert Cout == g.Cout
+    if routes is None:
+        routes = backward_routes(g, B, H, W)
+    d = g.desc(B, H, W, Ho, Wo, nhwc_ld(x0), nhwc_ld(x1) if x1 is not None else 0)
     L = _lib.lib()
     if out is not None and tuple(out.shape) == (Cout, g.Cin, g.k, g.k) and out.is_contiguous() and out.dtype == torch.float32:
         dw = out
@@ -885,47 +931,35 @@ def conv_wgrad(g, x0, x1, dy, wino_v=None, out=None):
         dw = torch.empty((Cout, g.Cin, g.k, g.k), dtype=torch.float32, device=dy.device)
     flops = 2.0 * B * Ho * Wo * Cout * g.CinAlg * g.k * g.k
     flops_x = flops * g.Cin / g.CinAlg * _live_tap_frac(g, H, W, wgrad=True)
-    if wino_v is None and (Ho, Wo) == (H, W) and winograd_fused_wgrad_ok(g, B, H, W):
-        nbytes = L.segsde_conv2d_wgrad_winograd_fused_workspace(ctypes.byref(d))
-        if nbytes:
-            ws = _ws(nbytes, dy)
-            rc = _timed("conv_wgrad", flops, dy, lambda: L.segsde_conv2d_wgrad_winograd_fused(
-                ctypes.byref(d), _p(_f32(x0)), _p(x1), _p(_f32(dy)), nhwc_ld(dy), _p(dw), _p(ws), nbytes, _stream(dy)),
-                _tag(g, H, W) + " wino-fused",
-                # (9 / 36 on the upsampled source's channels where the launch skips its zero positions: that source carries at
-                # least half of the channels, csrc/winograd_wgrad.hip)
-                executed=flops * ((9.0 * g.C0 + 16.0 * g.C1) / (36.0 * g.Cin)
-                                  if (g.up0 and 2 * g.C0 >= g.Cin) else 16.0 / 36.0))
-            if rc == 0:
-                WINO_FUSED_TAKEN["wgrad"] += 1
-                return dw
-            if rc != -4:
-                check(rc, "conv2d_wgrad_winograd_fused")
-    if not g.up0 and winograd_ok(g, B, H, W) and (Ho, Wo) == (H, W):
-        nbytes = L.segsde_conv2d_wgrad_winograd_workspace(ctypes.byref(d))
-        if nbytes:
-            ws = _ws(nbytes, dy)
-            rc = _timed("conv_wgrad", flops, dy, lambda: L.segsde_conv2d_wgrad_winograd(
-                ctypes.byref(d), _p(x0), _p(x1), _p(_f32(dy)), nhwc_ld(dy), _p(wino_v), _p(dw), _p(ws), nbytes, _stream(dy)),
-                _tag(g, H, W) + " wino", executed=flops * 16.0 / 36.0)
-            if rc == 0:
-                WINOGRAD_TAKEN["wgrad"] += 1
-                return dw
-            if rc != -4:
-                check(rc, "conv2d_wgrad_winograd")
-    if upfold_ok(g, B * Ho * Wo):
-        nbytes = L.segsde_conv2d_wgrad_upfold_workspace(ctypes.byref(d))
-        if nbytes:
-            ws = _ws(nbytes, dy)
-            rc = _timed("conv_wgrad", flops, dy, lambda: L.segsde_conv2d_wgrad_upfold(
-                ctypes.byref(d), _p(x0), _p(x1), _p(_f32(dy)), nhwc_ld(dy), _p(dw), _p(ws), nbytes, _stream(dy)),
-                _tag(g, H, W) + " fold", executed=flops * _fold_frac(g))
-            if rc == 0:
-                UPFOLD_TAKEN["wgrad"] += 1
-                _note_compute(d, 6, "wgrad")
-                return dw
-            if rc != -4:
-                check(rc, "conv2d_wgrad_upfold")
+    same_map = (Ho, Wo) == (H, W)
+
+    def attempt(workspace, launch, what, suffix, executed, x0p, *extra):
+        """one route: its workspace size (0: it does not take this descriptor), then the launch"""
+        nbytes = workspace(ctypes.byref(d))
+        if not nbytes:
+            return False
+        ws = _ws(nbytes, dy)
+        return _taken(what, "conv_wgrad", flops, dy, lambda: launch(
+            ctypes.byref(d), x0p, _p(x1), _p(_f32(dy)), nhwc_ld(dy), *extra, _p(dw), _p(ws), nbytes, _stream(dy)),
+            _tag(g, H, W) + suffix, executed=executed)
+
+    # (one-kernel: 9 / 36 on the upsampled source's channels where the launch skips its zero positions -- that source carries at
+    # least half of the channels, csrc/winograd_wgrad.hip)
+    if wino_v is None and routes.wgrad_fused and same_map and attempt(
+            L.segsde_conv2d_wgrad_winograd_fused_workspace, L.segsde_conv2d_wgrad_winograd_fused, "conv2d_wgrad_winograd_fused",
+            " wino-fused", flops * ((9.0 * g.C0 + 16.0 * g.C1) / (36.0 * g.Cin) if (g.up0 and 2 * g.C0 >= g.Cin) else 16.0 / 36.0),
+            _p(_f32(x0))):
+        WINO_FUSED_TAKEN["wgrad"] += 1
+        return dw
+    if routes.wgrad_grouped and same_map and attempt(L.segsde_conv2d_wgrad_winograd_workspace, L.segsde_conv2d_wgrad_winograd,
+                                                     "conv2d_wgrad_winograd", " wino", flops * 16.0 / 36.0, _p(x0), _p(wino_v)):
+        WINOGRAD_TAKEN["wgrad"] += 1
+        return dw
+    if routes.wgrad_upfold and attempt(L.segsde_conv2d_wgrad_upfold_workspace, L.segsde_conv2d_wgrad_upfold, "conv2d_wgrad_upfold",
+                                       " fold", flops * _fold_frac(g), _p(x0)):
+        UPFOLD_TAKEN["wgrad"] += 1
+        _note_compute(d, 6, "wgrad")
+        return dw
     nbytes = L.segsde_conv2d_wgrad_workspace(ctypes.byref(d))
     ws = _ws(nbytes, dy)
     _timed("conv_wgrad", flops, dy, lambda: check(L.segsde_conv2d_wgrad(
@@ -940,16 +974,8 @@ def conv_compute_taken(g, B, H, W, direction, fold=False):
     input with dense tensors (segsde_conv_compute_taken: the launchers' own dispatch, nothing is launched).  direction: "fwd",
     "dgrad", "wgrad"; fold: the upsample-folded entry point of that direction (g.up0).  Says nothing about the Winograd routes,
     which are fp32 kernels and are chosen before the direct ones (winograd_ok, winograd_fused_ok ...)."""
-    Ho, Wo = g.out_hw(H, W)
-    pm = PAD_REFLECT if g.reflect else PAD_ZERO
     code = {"fwd": 0, "dgrad": 1, "wgrad": 2}[direction] | (4 if fold else 0)
-    if direction == "dgrad" and not fold:
-        d = ConvDesc(B=B, H=Ho, W=Wo, C0=g.Cout, C1=0, ld0=g.Cout, ld1=0, up0=0, Ho=H, Wo=W, Cout=g.Cin, ldy=g.C0, ldy2=g.C1, nsplit=g.C0,
-                     KH=g.k, KW=g.k, stride=1, dil=g.dil, pad=(g.k - 1) * g.dil - g.pad, pad_mode=PAD_REFLECT_ADJOINT if g.reflect else PAD_ZERO,
-                     in_div=g.stride, act=0, sum2x2=0, accumulate=0, compute=g.compute)
-    else:
-        d = ConvDesc(B=B, H=H, W=W, C0=g.C0, C1=g.C1, ld0=g.C0, ld1=g.C1, up0=int(g.up0), Ho=Ho, Wo=Wo, Cout=g.Cout, ldy=g.Cout, ldy2=0,
-                     nsplit=0, KH=g.k, KW=g.k, stride=g.stride, dil=g.dil, pad=g.pad, pad_mode=pm, in_div=1, act=0, sum2x2=0, compute=g.compute)
+    d = g.dgrad_desc(B, H, W) if (direction == "dgrad" and not fold) else g.desc(B, H, W)
     return int(_lib.lib().segsde_conv_compute_taken(ctypes.byref(d), code))
 
 
@@ -1066,27 +1092,22 @@ def bn_apply_mask(x, mean, invstd, gamma, beta, residual=None, act="none"):
     nbytes = (8.0 + (4.0 if residual is not None else 0.0)) * M * C
     if C % 4 == 0:
         mask = torch.empty(L.segsde_bn_mask_words(M, C), dtype=torch.int32, device=x.device)
-        code = _timed('hbm_bn_apply', nbytes + 0.125 * M * C, x, lambda: L.segsde_bn_apply_mask(
-            _p(x), ld, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), ldr, _p(y), _rows(y)[2], ACT[act], 0.0, 0,
-            _p(mask), _stream(x)))
-        if code == 0:
+        if _taken("bn_apply_mask", 'hbm_bn_apply', nbytes + 0.125 * M * C, x, lambda: L.segsde_bn_apply_mask(
+                _p(x), ld, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), ldr, _p(y), _rows(y)[2], ACT[act], 0.0, 0,
+                _p(mask), _stream(x))):
             return y, mask
-        if code != -4:
-            check(code, "bn_apply_mask")
     _timed('hbm_bn_apply', nbytes, x, lambda: check(L.segsde_bn_apply(_p(x), ld, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), ldr, _p(y),
                                                                        _rows(y)[2], ACT[act], 0.0, 0, _stream(x)), "bn_apply"))
     return y, None
 
 
-BN_MASK_USED = _Slot(False)       # did the last bn_backward(mask=...) read the packed bits (functional.py counts from this)
-
-
 def bn_backward(dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, batch_stats=True, need_dx=True,
-                need_dres=False, beta=None, dgamma_out=None, dbeta_out=None, mask=None):
+                need_dres=False, beta=None, dgamma_out=None, dbeta_out=None, mask=None, note=None):
     """y=None selects the remask mode of segsde_bn_backward (act none / plain ReLU: mask recomputed from x, beta needed).
     dgamma_out / dbeta_out: dense [C] tensors to write into (gradient-bucket slices, ddp.grad_destination).
     mask: the bits bn_apply_mask packed (ReLU, no dropout): segsde_bn_backward_mask reads them in place of y, with bit-identical
-    results; where that entry does not take the call (pitch / alignment of dy or of the destinations) the saved y is read."""
+    results; where that entry does not take the call (pitch / alignment of dy or of the destinations) the saved y is read.
+    note: a dict that receives "mask_used": did this call read the packed bits."""
     M, C, ldx = _rows(x)
     L = _lib.lib()
 
@@ -1098,18 +1119,18 @@ def bn_backward(dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, b
     dres = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dres else None
     nb = L.segsde_bn_backward_workspace(M, C)
     ws = _ws(nb, x)
-    BN_MASK_USED[0] = False
+    if note is not None:
+        note["mask_used"] = False
     if mask is not None:
         # both passes read dy, x and 1 bit per element: reduce 8.125, apply 8.125 + the tensors it writes
-        code = _timed('hbm_bn_backward', (16.25 + (4.0 if need_dx else 0.0) + (4.0 if need_dres else 0.0)) * M * C, x,
-                      lambda: L.segsde_bn_backward_mask(_p(_f32(dy)), _rows(dy)[2], _p(mask), _p(x), ldx, M, C, _p(mean), _p(invstd),
-                                                        _p(gamma), ACT[act], float(drop_p), int(batch_stats), _p(dgamma), _p(dbeta),
-                                                        _p(dx), C, _p(dres), C, _p(ws), nb, _stream(x)))
-        if code == 0:
-            BN_MASK_USED[0] = True
+        # (without a saved y there is nothing to fall back on: a decline is an error then)
+        if _taken("bn_backward_mask", 'hbm_bn_backward', (16.25 + (4.0 if need_dx else 0.0) + (4.0 if need_dres else 0.0)) * M * C, x,
+                  lambda: L.segsde_bn_backward_mask(_p(_f32(dy)), _rows(dy)[2], _p(mask), _p(x), ldx, M, C, _p(mean), _p(invstd),
+                                                    _p(gamma), ACT[act], float(drop_p), int(batch_stats), _p(dgamma), _p(dbeta),
+                                                    _p(dx), C, _p(dres), C, _p(ws), nb, _stream(x)), may_decline=y is not None):
+            if note is not None:
+                note["mask_used"] = True
             return dx, dres, dgamma, dbeta
-        if code != -4 or y is None:
-            check(code, "bn_backward_mask")
     _timed('hbm_bn_backward', (8.0 + (4.0 if y is not None else 0.0) + (4.0 if need_dx else 0.0) + (4.0 if need_dres else 0.0)) * M * C + 8.0 * M * C, x, lambda: check(L.segsde_bn_backward(_p(_f32(dy)), _rows(dy)[2], _p(y), _rows(y)[2] if y is not None else ldx, _p(x), ldx, M, C,
                                _p(mean), _p(invstd), _p(gamma), _p(beta), ACT[act], float(drop_p), int(seed), int(batch_stats), _p(dgamma), _p(dbeta),
                                _p(dx), C, _p(dres), C, _p(ws), nb, _stream(x)), "bn_backward"))

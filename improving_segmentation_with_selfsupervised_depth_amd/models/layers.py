@@ -64,9 +64,9 @@ class weight_pack_scope:
             d["_packs"], d["_pack_key"] = pk, (scope_id, w._version, w.data_ptr(), w.device)
         # the Winograd-transformed packs of the 3x3 / stride-1 convolutions with many channels, likewise in one launch
         # (the one-kernel route's packs have their own layout: two launches, one per layout)
+        layout = [H.winograd_prepack_layout(m) for m in convs]
         for kn in (True, False):
-            wino = [m for m in convs if (H.winograd_fused_static_ok(m) if kn
-                                         else (H.winograd_static_ok(m) and not H.winograd_fused_static_ok(m)))]
+            wino = [m for m, lay in zip(convs, layout) if lay is kn]
             if wino:
                 for m, pk in zip(wino, H.winograd_packs_multi([m.weight for m in wino], kn=kn)):
                     w = m.weight
@@ -266,8 +266,7 @@ def _folded_forward(conv, bn, x, residual, act, image_norm):
         # BasicBlock.conv2: the Winograd geometry, and the Winograd routes take no residual operand -- this pair keeps its
         # normalisation pass whatever route its size selects (one rule, so the count does not depend on the image size)
         return None
-    kn = H.winograd_fused_ok(g, B, Hh, W)
-    wino = kn or H.winograd_ok(g, B, Hh, W)
+    routes = H.forward_routes(g, B, Hh, W, skip_grad=False)
     e = _folded(conv, bn)
     pk = ("pack", c0)
     if pk not in e:
@@ -280,12 +279,12 @@ def _folded_forward(conv, bn, x, residual, act, image_norm):
             residual = Fn._c(residual)
         return H.conv_forward(g, x, None, e[pk], e["b"], act, residual=residual)
     wino_f = None
-    if wino:
-        wk = ("wino", bool(kn))
+    if routes.fused or routes.grouped:
+        wk = ("wino", routes.fused)
         if wk not in e:
-            e[wk] = H.winograd_pack(e["w"], kn=bool(kn))[0]
+            e[wk] = H.winograd_pack(e["w"], kn=routes.fused)[0]
         wino_f = e[wk]
-    return H.conv_forward(g, x, None, e[pk], e["b"], act, wino=wino_f)
+    return H.conv_forward(g, x, None, e[pk], e["b"], act, wino=wino_f, routes=routes)
 
 
 def conv_bn(conv, bn, x, residual=None, act="none", drop_p=0.0, bn_grad_box=None, image_norm=None, **conv_kwargs):

@@ -1477,13 +1477,15 @@ def _run_winograd_fused_cases(device, shapes):
             assert H.WINO_FUSED_TAKEN["dgrad_refl"] == n0["dgrad_refl"] + 1, what + ": the one-kernel route declined"
             e_2 = float((nchw(dx2).double().cpu() - wantg).abs().max())
             assert e_2 <= 3 * e_d + 1e-6 * scg, (what, "border kernel", e_2, e_d, scg)
-            dz, _ = H.conv_dgrad(g, dyd, wdp, wd_, (Hh, W), wino=ud, actgrad=(ad, "elu"), wfpack=wfp)
-            assert H.ACTGRAD_FUSED[0] and H.WINO_FUSED_TAKEN["dgrad_actgrad"] == n0["dgrad_actgrad"] + 1
+            note = {}
+            dz, _ = H.conv_dgrad(g, dyd, wdp, wd_, (Hh, W), wino=ud, actgrad=(ad, "elu"), wfpack=wfp, note=note)
+            assert note["actgrad_fused"] and H.WINO_FUSED_TAKEN["dgrad_actgrad"] == n0["dgrad_actgrad"] + 1
             assert_close(nchw(dz).cpu(), (wantg * deriv).float(), rtol=1e-4, atol=3 * e_d + 1e-6 * scg, what=what + " x ELU'")
             base = torch.randn(B, Hh, W, C, generator=gen).to(device)
             acc = base.clone()
-            dz2, _ = H.conv_dgrad(g, dyd, wdp, wd_, (Hh, W), wino=ud, actgrad=(ad, "elu"), accumulate_into=acc, wfpack=wfp)
-            assert dz2 is acc and H.ACTGRAD_FUSED[0]
+            note = {}
+            dz2, _ = H.conv_dgrad(g, dyd, wdp, wd_, (Hh, W), wino=ud, actgrad=(ad, "elu"), accumulate_into=acc, wfpack=wfp, note=note)
+            assert dz2 is acc and note["actgrad_fused"]
             assert_close(acc, base + dz, rtol=1e-6, atol=1e-6 * scg, what=what + " x ELU', accumulated")
             # zero padding + derivative (layer1 / layer2 never need it, but the epilogue is the same code)
             g0 = H.ConvGeom(C, Co, 3, 1, 1, 1, False, 0, False)
@@ -1548,8 +1550,10 @@ def _run_winograd_fused_cases(device, shapes):
                         assert e_w <= 3 * e_d + 2e-6 * sc, (what, tag, e_w, e_d, sc)
                     base = torch.randn(B, Hh, W, C1, generator=gen).to(device)
                     acc = base.clone()
-                    _, a1 = H.conv_dgrad(g, dyd, wdp, wd_, (Hh, W), fold=fold, wino=ud, wfpack=wfp, accumulate_skip_into=acc, need0=False)
-                    assert a1 is acc and H.SKIP_ACCUMULATED[0]
+                    note = {}
+                    _, a1 = H.conv_dgrad(g, dyd, wdp, wd_, (Hh, W), fold=fold, wino=ud, wfpack=wfp, accumulate_skip_into=acc, need0=False,
+                                         note=note)
+                    assert a1 is acc and note["skip_accumulated"]
                     assert_close(acc, base + f1, rtol=1e-6, atol=1e-6 * float(f1.abs().max()), what=what + ", accumulated onto the collector")
             finally:
                 H.UPFOLD_MIN_SAVED_MACS = old_fm
@@ -1886,3 +1890,171 @@ def run_torch_ops(device, golden):
     dm = ops.depthcomp_mask(d(depths), 0.05, 0.3)
     want = ((depths >= torch.roll(depths, -1, 0) - 0.05) & (depths >= 0.3)).long()
     assert torch.equal(dm.cpu(), want)
+
+
+# ---------------------------------------------------------------------------------------------
+# the convolution dispatch as a whole: which launches, in which order, a fixed set of layers makes (the routes of hipops.conv_forward
+# / conv_dgrad / conv_wgrad and the BatchNorm passes around them), pinned against tests/golden/conv_launch_sequence.json
+# ---------------------------------------------------------------------------------------------
+LAUNCH_SEQUENCE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_launch_sequence.json")
+
+
+def conv_launch_sequence(device):
+    """[[kind, tag, flops, executed], ...] of every timed launch of forward + backward through Conv2d / ConvFn for small layers of
+    every route family, once under the default gate constants and once with the size floors at 0 (rows of kind "case" name the
+    layer that follows, a row of kind "fusions" closes each pass with the hand-offs functional.py counted in it)"""
+    from improving_segmentation_with_selfsupervised_depth_amd import functional as Fn
+    from improving_segmentation_with_selfsupervised_depth_amd.models import layers as L
+    from improving_segmentation_with_selfsupervised_depth_amd.models.resnet_encoder import BasicBlock, Bottleneck
+    log = []
+
+    def recorder(kind, flops, like, launch, tag="", executed=None):
+        log.append([kind, tag, float(flops), float(flops if executed is None else executed)])
+        return launch()
+
+    gen = torch.Generator().manual_seed(41)
+
+    def rnd(*shape, grad=True):
+        t = torch.randn(*shape, generator=gen).to(device)
+        return (t.requires_grad_(True) * 1.0) if grad else t          # a non-leaf that requires a gradient, like an activation
+
+    def conv(cin, cout, k, **kw):
+        return L.Conv2d(cin, cout, k, **kw).to(device).train()
+
+    def back(*ys):
+        torch.autograd.backward(ys, [torch.ones_like(y) for y in ys])
+
+    def case(name):
+        log.append(["case", name, 0.0, 0.0])
+
+    def layers():
+        case("3x3 64->64 -> BatchNorm (statistics from the epilogue)")
+        c, bn = conv(64, 64, 3, padding=1, bias=False), L.BatchNorm2d(64).to(device).train()
+        back(bn(c(rnd(1, 8, 16, 64)), act="relu"))
+        case("mirrored 3x3 64->64 + ELU twice (activation derivative in the consumer's data-gradient)")
+        c1, c2 = conv(64, 64, 3, padding=1, reflect=True), conv(64, 64, 3, padding=1, reflect=True)
+        back(c2(c1(rnd(1, 8, 16, 64), act="elu"), act="elu"))
+        case("BasicBlock 64 (data-gradient accumulated onto the residual path)")
+        back(BasicBlock(64, 64).to(device).train()(rnd(1, 8, 16, 64)))
+        for c1_ in (64, 32):
+            case("two decoders on [up(64)|%d]->64 mirrored + ELU (skip gradients accumulated)" % c1_)
+            (v1, v2), box = Fn.fan_feature(rnd(1, 16, 32, c1_), 0, 2)
+            ca, cb = conv(64 + c1_, 64, 3, padding=1, reflect=True), conv(64 + c1_, 64, 3, padding=1, reflect=True)
+            back(ca(rnd(1, 8, 16, 64), v1, True, act="elu", skip_box=box), cb(rnd(1, 8, 16, 64), v2, True, act="elu", skip_box=box))
+        case("[up(64)|0]->64 mirrored + ELU")
+        back(conv(64, 64, 3, padding=1, reflect=True)(rnd(1, 8, 16, 64), None, True, act="elu"))
+        case("3x3 512->512")
+        back(conv(512, 512, 3, padding=1, bias=False)(rnd(1, 8, 8, 512)))
+        case("dilated 3x3 256->256 d=2")
+        back(conv(256, 256, 3, padding=2, dilation=2, bias=False)(rnd(1, 8, 8, 256)))
+        case("two sources [128|128]->256 mirrored")
+        back(conv(256, 256, 3, padding=1, reflect=True)(rnd(1, 8, 16, 128), rnd(1, 8, 16, 128), act="elu"))
+        case("3x3 64->64 on an odd map 7x16")
+        back(conv(64, 64, 3, padding=1)(rnd(1, 7, 16, 64)))
+        case("mirrored 3x3 64->64 on a 6x4 map")
+        back(conv(64, 64, 3, padding=1, reflect=True)(rnd(1, 6, 4, 64)))
+        case("1x1 64->128")
+        back(conv(64, 128, 1, bias=False)(rnd(1, 8, 16, 64)))
+        case("stride-2 3x3 64->128")
+        back(conv(64, 128, 3, stride=2, padding=1, bias=False)(rnd(1, 8, 16, 64)))
+        case("7x7 s2 stem, 4 channels carrying 3")
+        back(conv(3, 64, 7, stride=2, padding=3, bias=False)(rnd(1, 16, 32, 4, grad=False)))
+        case("mirrored 3x3 64->1 + sigmoid")
+        back(conv(64, 1, 3, padding=1, reflect=True)(rnd(1, 8, 16, 64), act="sigmoid"))
+        case("no_grad, packs of a weight_pack_scope(model)")
+        net = torch.nn.ModuleList([conv(64, 64, 3, padding=1, bias=False), conv(128, 64, 3, padding=1, reflect=True),
+                                   conv(256, 256, 3, padding=1, bias=False), conv(64, 128, 1)])
+        with torch.no_grad(), L.weight_pack_scope(net):
+            net[0](rnd(1, 8, 16, 64, grad=False))
+            net[1](rnd(1, 8, 16, 64, grad=False), rnd(1, 16, 32, 64, grad=False), True, act="elu")
+            net[2](rnd(1, 8, 8, 256, grad=False))
+            net[3](rnd(1, 8, 16, 64, grad=False))
+        case("the same layers with gradients, same scope")
+        with L.weight_pack_scope(net):
+            back(net[0](rnd(1, 8, 16, 64)), net[1](rnd(1, 8, 16, 64), rnd(1, 16, 32, 64), True, act="elu"), net[2](rnd(1, 8, 8, 256)))
+        case("frozen BatchNorm folded into the convolutions of a BasicBlock and a Bottleneck (no_grad)")
+        with torch.no_grad(), Fn.frozen_bn_fold():
+            BasicBlock(64, 64).to(device).eval()(rnd(1, 8, 16, 64, grad=False))
+            Bottleneck(64, 16).to(device).eval()(rnd(1, 8, 16, 64, grad=False))
+        case("mirrored 3x3 64->64 + ELU, split-bf16 operands")
+        with Fn.conv_compute("bf16x9"):
+            back(conv(64, 64, 3, padding=1, reflect=True)(rnd(1, 8, 16, 64), act="elu"))
+        case("mirrored 3x3 64->64 + ELU, fp16 operands")
+        old16 = H.COMPUTE_F16[0]
+        H.COMPUTE_F16[0] = True
+        try:
+            back(conv(64, 64, 3, padding=1, reflect=True)(rnd(1, 8, 16, 64), act="elu"))
+        finally:
+            H.COMPUTE_F16[0] = old16
+
+    floors = ("WINOGRAD_MIN_MACS", "UPFOLD_MIN_SAVED_MACS", "WINO_FUSED_REFLECT_DGRAD_MIN_PIX")
+    old = {n: getattr(H, n) for n in floors}
+    old_timed, H._timed = H._timed, recorder
+    old_fusions = dict(Fn.FUSIONS)
+    try:
+        for zero in (False, True):
+            case("== size floors at 0 ==" if zero else "== default gate constants ==")
+            for n in floors:
+                setattr(H, n, 0 if zero else old[n])
+            Fn.FUSIONS.clear()
+            layers()
+            log.append(["fusions", "; ".join("%s %d/%d" % (k, v["taken"], v["missed"]) for k, v in Fn.fusion_report().items()), 0.0, 0.0])
+    finally:
+        Fn.FUSIONS.clear()
+        Fn.FUSIONS.update(old_fusions)
+        H._timed = old_timed
+        for n in floors:
+            setattr(H, n, old[n])
+    return log
+
+
+def run_conv_launch_sequence(device):
+    import json
+    got = conv_launch_sequence(device)
+    with open(LAUNCH_SEQUENCE_GOLDEN) as f:
+        want = json.load(f)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a == b, ("launch %d differs" % i, a, b, [r[1] for r in got[:i] if r[0] == "case"][-1:])
+    assert len(got) == len(want), (len(got), len(want))
+    # the layers do reach every route family
+    tags = " ".join('"%s"' % r[1] for r in got)
+    for word in (" wino-fused", " wino\"", " fold", " res", "skip-of-", " up refl"):
+        assert word in tags, word
+
+
+
+def run_winograd_grouped_split_bf16_case(device):
+    """The grouped-GEMM Winograd forward and data-gradient are fp32 launches in every operand mode that takes the route: under
+    conv_compute("bf16x9") their results are bit-identical to the default mode's (the position GEMMs run on the implicit-GEMM kernel,
+    whose split-bf16 loop a descriptor with compute = 2 would select).  512 -> 512 at 1x8x8 under the default constants, and
+    64 -> 64 at 1x8x16 with the channel gate lowered and the one-kernel route off.  (The weight gradient's launch carries the
+    convolution's operand mode, as it always has: not part of this property.)"""
+    from improving_segmentation_with_selfsupervised_depth_amd import functional as Fn
+    gen = torch.Generator().manual_seed(77)
+    old = (H.WINOGRAD_MIN_CH, H.WINOGRAD_MIN_MACS, H.WINO_FUSED)
+    try:
+        for (B, Hh, W, C, Co, lowered) in ((1, 8, 8, 512, 512, False), (1, 8, 16, 64, 64, True)):
+            if lowered:
+                H.WINOGRAD_MIN_CH, H.WINOGRAD_MIN_MACS, H.WINO_FUSED = 32, 0.0, False
+            x = nhwc(torch.randn(B, C, Hh, W, generator=gen)).to(device).contiguous()
+            dy = nhwc(torch.randn(B, Co, Hh, W, generator=gen)).to(device).contiguous()
+            w = (torch.randn(Co, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(device)
+            uf, ud = H.winograd_pack(w)
+            wp, wdp = H.pack_weight_both(w)
+
+            def run():
+                g = H.ConvGeom(C, Co, 3, 1, 1, 1, False, 0, False)      # (reads the operand mode)
+                n0 = dict(H.WINOGRAD_TAKEN)
+                y = H.conv_forward(g, x, None, wp, None, wino=uf)
+                dx, _ = H.conv_dgrad(g, dy, wdp, w, (Hh, W), wino=ud)
+                assert all(H.WINOGRAD_TAKEN[k] == n0[k] + 1 for k in ("fwd", "dgrad")), ("the grouped route declined", g.compute)
+                return g.compute, y, dx
+            c0, y0, dx0 = run()
+            with Fn.conv_compute("bf16x9"):
+                c2, y2, dx2 = run()
+            assert (c0, c2) == (0, 2)
+            for a, b, what in ((y0, y2, "forward"), (dx0, dx2, "data-gradient")):
+                assert torch.equal(a, b), ("grouped Winograd %s differs between the f32 and the bf16x9 operand mode" % what,
+                                           (B, Hh, W, C, Co), float((a - b).abs().max()))
+    finally:
+        H.WINOGRAD_MIN_CH, H.WINOGRAD_MIN_MACS, H.WINO_FUSED = old

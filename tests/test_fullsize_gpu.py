@@ -703,8 +703,9 @@ def test_winograd_fused_decoder_fullsize_vs_direct(geom):
         assert float((yw - yd).abs().max()) <= 1e-5 * sc, (name, "forward", float((yw - yd).abs().max()), sc)
         del yw, yd
         if not (up or C1):
-            dxw, _ = H.conv_dgrad(g, dy, wd, w, (Hh, W), wino=ud, actgrad=(x0, "elu"), wfpack=wp)
-            assert H.WINO_FUSED_TAKEN["dgrad_refl"] == n0["dgrad_refl"] + 1 and H.ACTGRAD_FUSED[0], name + ": data-gradient declined"
+            note = {}
+            dxw, _ = H.conv_dgrad(g, dy, wd, w, (Hh, W), wino=ud, actgrad=(x0, "elu"), wfpack=wp, note=note)
+            assert H.WINO_FUSED_TAKEN["dgrad_refl"] == n0["dgrad_refl"] + 1 and note["actgrad_fused"], name + ": data-gradient declined"
             dxd, _ = H.conv_dgrad(g, dy, wd, w, (Hh, W), actgrad=(x0, "elu"))
             sc = float(dxd.abs().max())
             assert float((dxw - dxd).abs().max()) <= 1e-5 * sc, (name, "data-gradient", float((dxw - dxd).abs().max()), sc)

@@ -159,3 +159,11 @@ def test_dropout_layer():
 
 def test_bn_stats_from_partials_plans():
     KC.run_bn_partials_case("cpu")
+
+
+def test_conv_launch_sequence():
+    KC.run_conv_launch_sequence("cpu")
+
+
+def test_winograd_grouped_route_is_fp32_in_split_bf16_mode():
+    KC.run_winograd_grouped_split_bf16_case("cpu")
