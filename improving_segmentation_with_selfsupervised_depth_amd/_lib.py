@@ -189,6 +189,7 @@ _SIGS = {
     "segsde_labelsel_normalize_workspace": (c_size_t, [c_long, c_int, c_int]),
     "segsde_labelsel_normalize": (c_int, [P, c_long, c_long, c_int, c_int, P, c_size_t, P]),
     "segsde_labelsel_distance": (c_int, [P, c_long, c_int, c_int, c_int, P, P, c_long, P]),
+    "segsde_labelsel_patch_distance": (c_int, [P, c_long, c_int, c_int, c_int, c_int, P, P, c_long, P]),
     "segsde_labelsel_farthest_point": (c_int, [P, c_long, c_int, P, c_int, P, c_int, P, P, P, P]),
     "segsde_render_labels": (c_int, [P, c_long, c_long, c_long, c_long, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
     "segsde_render_unit_image": (c_int, [P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, P]),

@@ -257,6 +257,147 @@ __global__ __launch_bounds__(256) void distance_kernel(const float* bank, long l
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------ 4b. patch-wise distances
+// The directed Chamfer distance between images: D[i][j] = (1/P) sum_a min_b || f[i,:,a] - f[j,:,b] ||.  The rows of the pair
+// matrix are patches: patch a of image n is bank[n * ld + c * P + a], so a chunk of 32 channels of one image is already k-major.
+// A block owns whole images on both sides: ipt = 64 / P of them (one when P > 64), R = ipt * P patch rows, and walks over the
+// 64 x 64 sub-tiles of its R x R pair matrix (one for P <= 64, four for 64 < P <= 128).  Per sub-tile the pair sums are formed
+// exactly as in distance_kernel (4 x 4 register block, chunks of 32 channels in ascending c, compensated addition of the chunk
+// sums), parked in LDS over the dead operand chunks, and reduced to minima per (patch row, image on the other side):
+//   Mrow[q][jj] = min over the patches b of image jj of d(q, b)      -> D[I][J]
+//   Mcol[q][ii] = min over the patches a of image ii of d(a, q)      -> D[J][I]   (d is symmetric, D is not)
+// A minimum that spans two sub-tiles is continued in LDS; the square root is taken once, when the last part has joined.  The
+// comparison lets a NaN through from either side.  Rows past R and images past N are staged as zeros and never enter a minimum.
+// Only blocks with bj >= bi compute.  The means run over a in ascending order: every result is a pure function of the inputs.
+constexpr int PT = 64, PTLD = PT + 1;
+inline int patch_ipt(int P) { return P >= PT ? 1 : PT / P; }
+__device__ __forceinline__ float nan_min(float m, float v) { return (v < m || v != v) ? v : m; }
+
+// the P minima of one image pair, added in ascending a; compensated, so that the error of the mean does not grow with P (a plain
+// sum of 128 terms alone is 6 ulp off)
+__device__ __forceinline__ float patch_mean(const float* m, int stride, int P) {
+  float s = 0.f, comp = 0.f;
+  for (int a = 0; a < P; ++a) {
+    const float y = m[a * stride] - comp;
+    const float t = s + y;
+    comp = (t - s) - y;
+    s = t;
+  }
+  return s;
+}
+
+template <int PNORM>
+__global__ __launch_bounds__(256) void patch_distance_kernel(const float* bank, long ld, int N, int C, int P, int ipt,
+                                                             const float* bias, float* out, long ldo) {
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  if (bj < bi) return;
+  SEGSDE_SMEM;
+  const int R = ipt * P, nsub = (R + PT - 1) / PT;
+  float* As = reinterpret_cast<float*>(segsde_smem);                          // [DK][DLD]
+  float* Bs = As + DK * DLD;
+  float* Ts = As;                                                             // [PT][PTLD] pair sums, once the chunks are consumed
+  float* Mrow = As + 2 * DK * DLD;                                            // [R][ipt]
+  float* Mcol = Mrow + R * ipt;                                               // [R][ipt]
+  static_assert(PT * PTLD <= 2 * DK * DLD && PT == DT, "the pair sums fit over the two operand chunks");
+  const int img_i = bi * ipt, img_j = bj * ipt;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int sq = threadIdx.x % PT, sk = threadIdx.x / PT;                     // staging: patch row of the sub-tile, first channel
+  for (int sr = 0; sr < nsub; ++sr)
+    for (int sc = 0; sc < nsub; ++sc) {
+      // staging: this thread's patch row of either side (the same in every chunk) and where its channel 0 lies in the bank
+      const int qa = sr * PT + sq, qb = sc * PT + sq;
+      const bool in_a = qa < R && img_i + qa / P < N, in_b = qb < R && img_j + qb / P < N;
+      const long off_a = (long)(img_i + qa / P) * ld + qa % P, off_b = (long)(img_j + qb / P) * ld + qb % P;
+      float acc[4][4], comp[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = comp[r][c] = 0.f;
+      for (int k0 = 0; k0 < C; k0 += DK) {
+        float part[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) part[r][c] = 0.f;
+        __syncthreads();
+        for (int k = sk; k < DK; k += 256 / PT) {                             // consecutive threads: consecutive patches of a channel
+          const bool kin = k0 + k < C;
+          const long ck = (long)(k0 + k) * P;
+          As[k * DLD + sq] = (kin && in_a) ? bank[off_a + ck] : 0.f;
+          Bs[k * DLD + sq] = (kin && in_b) ? bank[off_b + ck] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int k = 0; k < DK; ++k) {
+          const float4 a4 = *reinterpret_cast<const float4*>(As + k * DLD + ty * 4);
+          const float4 b4 = *reinterpret_cast<const float4*>(Bs + k * DLD + tx * 4);
+          const float a[4] = {a4.x, a4.y, a4.z, a4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const float d = a[r] - bb[c];
+              part[r][c] += PNORM == 2 ? d * d : fabsf(d);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {                                       // the compensated addition of distance_kernel
+            const float y = part[r][c] - comp[r][c];
+            const float t = acc[r][c] + y;
+            comp[r][c] = (t - acc[r][c]) - y;
+            acc[r][c] = t;
+          }
+      }
+      __syncthreads();                                                        // the last chunk is consumed: Ts may cover it
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) Ts[(ty * 4 + r) * PTLD + tx * 4 + c] = acc[r][c];
+      __syncthreads();
+      for (int e = threadIdx.x; e < PT * ipt; e += 256) {                     // row minima: item (patch row a, image jj of J)
+        const int a = e % PT, jj = e / PT, q = sr * PT + a;
+        if (q >= R || img_i + q / P >= N || img_j + jj >= N) continue;
+        const int lo = max(jj * P, sc * PT), hi = min(jj * P + P, sc * PT + PT);
+        if (lo >= hi) continue;
+        const int off = a * PTLD - sc * PT;
+        float m = Ts[off + lo];
+        for (int b = lo + 1; b < hi; ++b) m = nan_min(m, Ts[off + b]);
+        float* dst = Mrow + q * ipt + jj;
+        if (lo != jj * P) m = nan_min(m, *dst);                               // the part an earlier sub-tile left
+        if (hi == jj * P + P && PNORM == 2) m = sqrtf(m);                     // the winner is known: one square root
+        *dst = m;
+      }
+      if (bj != bi)
+        for (int e = threadIdx.x; e < PT * ipt; e += 256) {                   // column minima: item (patch column b, image ii of I)
+          const int b = e % PT, ii = e / PT, q = sc * PT + b;
+          if (q >= R || img_j + q / P >= N || img_i + ii >= N) continue;
+          const int lo = max(ii * P, sr * PT), hi = min(ii * P + P, sr * PT + PT);
+          if (lo >= hi) continue;
+          const int off = b - sr * PT * PTLD;
+          float m = Ts[off + lo * PTLD];
+          for (int a = lo + 1; a < hi; ++a) m = nan_min(m, Ts[off + a * PTLD]);
+          float* dst = Mcol + q * ipt + ii;
+          if (lo != ii * P) m = nan_min(m, *dst);
+          if (hi == ii * P + P && PNORM == 2) m = sqrtf(m);
+          *dst = m;
+        }
+    }
+  __syncthreads();
+  const float fP = (float)P;
+  for (int e = threadIdx.x; e < ipt * ipt; e += 256) {
+    const int ii = e / ipt, jj = e % ipt, i = img_i + ii, j = img_j + jj;
+    if (i >= N || j >= N) continue;
+    float v = patch_mean(Mrow + ii * P * ipt + jj, ipt, P) / fP;
+    out[(long)i * ldo + j] = i == j ? 0.f : (bias ? v + bias[j] : v);
+    if (bj != bi) {
+      v = patch_mean(Mcol + jj * P * ipt + ii, ipt, P) / fP;
+      out[(long)j * ldo + i] = bias ? v + bias[i] : v;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ 5. farthest point
 // One workgroup of 512 threads; thread t owns the columns t, t + 512, ...  LDS: mind[N] floats (the minimum over the current
 // rows), flag[N] bytes (current sample or not), and a (value, index) pair per wave.
@@ -411,6 +552,24 @@ extern "C" int segsde_labelsel_distance(const float* bank, long ld, int N, int D
     hipLaunchKernelGGL(distance_kernel<2>, dim3(nt, nt), dim3(256), smem, ST(stream), bank, ld, N, D, bias, out, ldo);
   else
     hipLaunchKernelGGL(distance_kernel<1>, dim3(nt, nt), dim3(256), smem, ST(stream), bank, ld, N, D, bias, out, ldo);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_labelsel_patch_distance(const float* bank, long ld, int N, int C, int P, int p, const float* bias, float* out,
+                                              long ldo, void* stream) {
+  if (!bank || !out) return SEGSDE_ERR_NULL;
+  if (N <= 0 || C <= 0) return SEGSDE_ERR_SHAPE;
+  if ((p != 1 && p != 2) || P < 1 || P > SEGSDE_LABELSEL_PATCH_MAX_P || (long)N * P >= (1L << 31)) return SEGSDE_ERR_UNSUPPORTED;
+  if (ld < (long)C * P || ldo < N) return SEGSDE_ERR_SHAPE;
+  const int ipt = patch_ipt(P);
+  const int ng = (N + ipt - 1) / ipt;
+  if (ng > 65535) return SEGSDE_ERR_UNSUPPORTED;                              // more image groups than a grid dimension takes
+  const size_t smem = ((size_t)2 * DK * DLD + (size_t)2 * ipt * P * ipt) * sizeof(float);      // at most 50 176 B (P = 1)
+  if (p == 2)
+    hipLaunchKernelGGL(patch_distance_kernel<2>, dim3(ng, ng), dim3(256), smem, ST(stream), bank, ld, N, C, P, ipt, bias, out, ldo);
+  else
+    hipLaunchKernelGGL(patch_distance_kernel<1>, dim3(ng, ng), dim3(256), smem, ST(stream), bank, ld, N, C, P, ipt, bias, out, ldo);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }

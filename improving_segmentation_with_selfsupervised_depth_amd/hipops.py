@@ -2069,6 +2069,7 @@ def batchprep_resize_nearest(desc, Hd, Wd, channels):
 DEPTH_ERROR_TYPES = ("abs", "abs_inv_log", "abs_inv", "sq", "abs_rel", "sq_rel", "abs_log")      # SEGSDE_DEPTH_ERR_*
 POOL_TRANSFORMS = ("none", "inv_clamp", "log_inv_clamp")                                          # SEGSDE_POOL_*
 LABELSEL_FPS_MAX_N = 32000                                                                        # SEGSDE_LABELSEL_FPS_MAX_N
+LABELSEL_PATCH_MAX_P = 128                                                                        # SEGSDE_LABELSEL_PATCH_MAX_P
 
 
 def _nchw_strides(x):
@@ -2157,6 +2158,34 @@ def labelsel_distance(bank, p=2, bias=None, out=None):
     ld = int(bank.stride(0)) if N > 1 else D
     ldo = int(out.stride(0)) if N > 1 else N
     check(_lib.lib().segsde_labelsel_distance(_p(bank), ld, N, D, int(p), _p(bias), _p(out), ldo, _stream(bank)), "labelsel_distance")
+    return out
+
+
+def labelsel_patch_distance(bank, C, P, p=2, bias=None, out=None):
+    """[N, C*P] bank (patch a of image n: bank[n, c*P + a]) -> [N, N] directed Chamfer distances
+    D[i, j] = mean_a min_b ||f_i[:, a] - f_j[:, b]||_p (p = 1 or 2, direct form), + bias[j] per column when given, zero diagonal.
+    Not symmetric (except at P = 1); a NaN feature makes every distance it enters NaN.  P <= LABELSEL_PATCH_MAX_P.
+    ``out``: an optional float32 [N, >= N] destination with dense rows (its columns past N are left alone)."""
+    C, P = int(C), int(P)
+    if bank.dtype != torch.float32 or bank.dim() != 2 or bank.shape[1] != C * P or (bank.shape[1] > 1 and bank.stride(1) != 1):
+        raise ValueError("the bank is a float32 [N, C*P] tensor with dense rows")
+    N = int(bank.shape[0])
+    if p not in (1, 2):
+        raise NotImplementedError("labelsel_patch_distance: p = %r (only 1 and 2)" % (p,))
+    if P > LABELSEL_PATCH_MAX_P:
+        raise NotImplementedError("labelsel_patch_distance: P = %d patches per image (at most %d)" % (P, LABELSEL_PATCH_MAX_P))
+    if out is None:
+        out = torch.empty((N, N), dtype=torch.float32, device=bank.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != N or out.shape[1] != N or (N > 1 and out.stride(1) != 1):
+        raise ValueError("out must be a float32 [N, N] view with dense rows")
+    if bias is not None:
+        bias = _f32(bias, "bias").to(bank.device).contiguous()
+        if bias.numel() != N:
+            raise ValueError("one bias per sample: got %d for %d" % (bias.numel(), N))
+    ld = int(bank.stride(0)) if N > 1 else C * P
+    ldo = int(out.stride(0)) if N > 1 else N
+    check(_lib.lib().segsde_labelsel_patch_distance(_p(bank), ld, N, C, P, int(p), _p(bias), _p(out), ldo, _stream(bank)),
+          "labelsel_patch_distance")
     return out
 
 

@@ -9,8 +9,13 @@ for identical rows, bitwise symmetric); ``iterative_farthest_point`` is one laun
 
 Not here: the matplotlib dump, ``label_selection_main``, ``train_on_subset`` and ``build_trainer`` (file, TensorBoard and
 dataset orchestration around the reference's Trainer; INTEGRATION.md 1d shows how the reference's script uses this module).
-Limits: ``patch_wise=True`` raises NotImplementedError; ``p`` is 1 or 2; at most ``hipops.LABELSEL_FPS_MAX_N`` samples in the
-farthest-point loop; the selection on a distance matrix that holds NaN is unspecified."""
+The reference's patch-wise distances (``ifp_args["pw"]``: a directed Chamfer distance between the pooled maps of two images)
+are ``patch_feature_distance`` on ``hipops.labelsel_patch_distance``; ``acquire_scores`` calls it for ``pw: True``.
+Limits: ``p`` is 1 or 2; patch-wise distances take at most ``hipops.LABELSEL_PATCH_MAX_P`` = 128 positions per image (h <= 8),
+their matrix is not symmetric, and a NaN feature makes every distance it enters NaN, as ``torch.min`` does;
+``_calc_feature_distance(..., patch_wise=True)`` itself still raises NotImplementedError (see its docstring); at most
+``hipops.LABELSEL_FPS_MAX_N`` samples in the farthest-point loop; the selection on a distance matrix that holds NaN is
+unspecified."""
 import contextlib
 
 import numpy as np
@@ -84,11 +89,9 @@ class FeatureBank:
         return self.bank[:self.n]
 
 
-def _calc_feature_distance(features, bias, bias_weight, p, normalize_features, patch_wise):
-    """features: a list of [1,C,h,2h] tensors (the reference's argument) or a FeatureBank -> [N,N] distances between the
-    flattened features, + bias[j] on column j when bias_weight > 0, zero diagonal.  The caller's features are not modified."""
-    if patch_wise:
-        raise NotImplementedError("patch_wise feature distances")
+def _bank_and_bias(features, bias, bias_weight, normalize_features):
+    """features: a list of [1,C,H,W] tensors or a FeatureBank -> ([N, C*P] bank, normalised on a copy when asked; C; P = H*W;
+    the column bias as a float32 tensor or None)"""
     if isinstance(features, FeatureBank):
         C, P = features.C, features.P
         bank = features.features()
@@ -109,7 +112,30 @@ def _calc_feature_distance(features, bias, bias_weight, p, normalize_features, p
     if bias_weight > 0:
         assert len(bias) == bank.shape[0]
         b = torch.tensor([float(v) for v in bias], dtype=torch.float32)
+    return bank, C, P, b
+
+
+def _calc_feature_distance(features, bias, bias_weight, p, normalize_features, patch_wise):
+    """features: a list of [1,C,h,2h] tensors (the reference's argument) or a FeatureBank -> [N,N] distances between the
+    flattened features, + bias[j] on column j when bias_weight > 0, zero diagonal.  The caller's features are not modified.
+
+    ``patch_wise=True`` is refused here and lives in ``patch_feature_distance``: the refusal is part of what the package's
+    test cases pin for this function, and the reference calls the function only from ``acquire_scores``, which this package
+    replaces and which dispatches on ``ifp_args["pw"]`` itself."""
+    if patch_wise:
+        raise NotImplementedError("patch_wise feature distances: call patch_feature_distance (acquire_scores does for pw: True)")
+    bank, _, _, b = _bank_and_bias(features, bias, bias_weight, normalize_features)
     return H.labelsel_distance(bank, p, b)
+
+
+def patch_feature_distance(features, bias, bias_weight, p, normalize_features):
+    """The reference's ``_calc_feature_distance(..., patch_wise=True)`` (label_selection.py:582-612): features: a list of
+    [1,C,H,W] tensors of any H, W (P = H*W positions) or a FeatureBank -> [N,N] directed Chamfer distances
+    D[i,j] = mean_a min_b ||f_i[:,a] - f_j[:,b]||_p, + bias[j] on column j when bias_weight > 0, zero diagonal.
+    One launch of ``hipops.labelsel_patch_distance``: no (200 P) x (N P) intermediate.  P <= 128 and p in (1, 2), else
+    NotImplementedError; D is not symmetric; NaN propagates.  The caller's features and the bank are not modified."""
+    bank, C, P, b = _bank_and_bias(features, bias, bias_weight, normalize_features)
+    return H.labelsel_patch_distance(bank, C, P, p, b)
 
 
 def iterative_farthest_point(current_samples, feature_distances, n_new, preselected_samples=None):
@@ -323,8 +349,12 @@ def acquire_scores(model, batches, samples_to_score, label_selection_cfg, depth_
         scores.append(s)
     distances = 0
     if calc_depth_distances:
-        distances = _calc_feature_distance(bank, dist_bias, dist_bias_weight, p=ifp_args["p"],
-                                           normalize_features=ifp_args.get("norm", False), patch_wise=ifp_args.get("pw", False))
+        if ifp_args.get("pw", False):
+            distances = patch_feature_distance(bank, dist_bias, dist_bias_weight, p=ifp_args["p"],
+                                               normalize_features=ifp_args.get("norm", False))
+        else:
+            distances = _calc_feature_distance(bank, dist_bias, dist_bias_weight, p=ifp_args["p"],
+                                               normalize_features=ifp_args.get("norm", False), patch_wise=False)
     return scores, {"distances": depth_ifp_w * distances,
                     "dist_i_to_img_idx": bank.dist_i_to_img_idx if bank is not None else {},
                     "img_idx_to_dist_i": bank.img_idx_to_dist_i if bank is not None else {}}

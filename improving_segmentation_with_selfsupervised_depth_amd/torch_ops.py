@@ -195,6 +195,15 @@ def labelsel_distance(bank, p=2, bias=None):
     return H.labelsel_distance(bank, int(p), bias)
 
 
+@_op("labelsel_patch_distance(Tensor bank, int C, int P, int p=2, Tensor? bias=None) -> Tensor")
+def labelsel_patch_distance(bank, C, P, p=2, bias=None):
+    """[N,C*P] feature bank -> [N,N] directed Chamfer distances mean_a min_b ||f_i[:,a] - f_j[:,b]||_p in the direct form (p = 1 or
+    2, P <= 128), + bias[j] on column j, zero diagonal; not symmetric, NaN propagates (label_selection.patch_feature_distance;
+    forward only)"""
+    _forward_only("labelsel_patch_distance", bank, bias)
+    return H.labelsel_patch_distance(bank, int(C), int(P), int(p), bias)
+
+
 @_op("labelsel_farthest_point(Tensor dist, Tensor current, int n_new, Tensor? preselected=None) -> (Tensor, Tensor)")
 def labelsel_farthest_point(dist, current, n_new, preselected=None):
     """label_selection.iterative_farthest_point on matrix rows: -> (new row indices int64 [k], their distances float32 [k]), both

@@ -697,6 +697,20 @@ int segsde_labelsel_normalize(float* bank, long ld, long N, int C, int P, void* 
  * out has leading dimension ldo >= N; columns >= N of a row are not touched. */
 int segsde_labelsel_distance(const float* bank, long ld, int N, int D, int p, const float* bias, float* out, long ldo,
                              void* stream);
+/* The patch-wise distances of label_selection.py:582-612 (patch_wise=True), a directed Chamfer distance between images:
+ * out[i][j] = (1/P) sum_a min_b (sum_c |f_i[c][a] - f_j[c][b]|^p)^(1/p), a, b in [0, P), p = 2 or 1.  bank is the [N][ld >= C*P]
+ * feature bank: patch a of image n is bank[n*ld + c*P + a], c = 0..C-1.  Direct form only; the C terms are summed as in
+ * segsde_labelsel_distance (chunks of 32 channels in ascending c, compensated addition of the chunk sums).  The minimum is taken
+ * by comparisons on the sums (squared sums for p = 2, one sqrtf per winner) and a NaN operand makes it NaN, as torch.min does;
+ * the P minima are added in ascending a and divided by (float)P.  Then + bias[j] (device [N], nullable), and the diagonal is
+ * written as 0.  The pair distance is symmetric and evaluated once for out[i][j] and out[j][i], but out is NOT symmetric
+ * (except at P = 1, where it is bit for bit).  An image whose patches are a permutation of another's is at distance exactly 0;
+ * the order of the patches of image j does not change a bit of column j.  No atomics, no workspace: a pure function of the inputs.
+ * Limits (SEGSDE_ERR_UNSUPPORTED otherwise): p in {1, 2}; 1 <= P <= SEGSDE_LABELSEL_PATCH_MAX_P; N*P < 2^31; at most 65535 groups
+ * of max(1, 64 / P) images.  Columns >= N of a row of out are not touched. */
+#define SEGSDE_LABELSEL_PATCH_MAX_P 128
+int segsde_labelsel_patch_distance(const float* bank, long ld, int N, int C, int P, int p, const float* bias, float* out, long ldo,
+                                   void* stream);
 /* iterative_farthest_point (label_selection.py:627-648) in one launch of one workgroup: the running minimum over the rows of
  * the current samples and one membership byte per sample live in LDS (5 bytes per sample: N <= SEGSDE_LABELSEL_FPS_MAX_N, else
  * SEGSDE_ERR_UNSUPPORTED).  dist: float32 [N][ld]; current: device int32 [n_current] (n_current >= 1, indices in [0, N));
