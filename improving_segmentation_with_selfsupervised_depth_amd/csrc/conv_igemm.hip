@@ -2119,8 +2119,7 @@ extern "C" int segsde_conv2d_dgrad_actgrad(const segsde_conv_desc* d, const floa
   // disparity heads (Cout = 1) and their data-gradients (one gradient channel in): HBM-bound stencil kernels
   const bool plain3x3 = d->KH == 3 && d->KW == 3 && d->stride == 1 && d->dil == 1 && d->pad == 1 && d->C1 == 0 && !d->up0 &&
                         d->in_div <= 1 && !d->sum2x2 && d->H == d->Ho && d->W == d->Wo;
-  if (plain3x3 && d->Cout == 1 && d->pad_mode != SEGSDE_PAD_REFLECT_ADJOINT && segsde_c1_supported(d->C0, d->ld0) &&
-      aligned16(x0) && aligned16(wpack))
+  if (plain3x3 && d->Cout == 1 && d->pad_mode != SEGSDE_PAD_REFLECT_ADJOINT && segsde_c1_forward_supported(d->C0) && aligned16(wpack))
     return probing() ? 0 : segsde_c1_forward(x0, d->ld0, d->B, d->H, d->W, d->C0, wpack, bias, d->pad_mode == SEGSDE_PAD_REFLECT, d->act, y,
                              d->ldy, stream);
   if (plain3x3 && d->C0 == 1 && d->pad_mode != SEGSDE_PAD_REFLECT && !bias && d->act == 0 &&

@@ -2,6 +2,8 @@
 #pragma once
 #include <stddef.h>
 bool segsde_c1_supported(int C, int ldx);
+// the forward: x at any pixel pitch >= C and any base alignment (wpack 16-byte aligned)
+bool segsde_c1_forward_supported(int C);
 size_t segsde_c1_wgrad_workspace(int C);
 int segsde_c1_forward(const float* x, int ldx, int B, int H, int W, int C, const float* wpack, const float* bias, int reflect,
                       int act, float* y, int ldy, void* stream);

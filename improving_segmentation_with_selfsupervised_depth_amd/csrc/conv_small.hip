@@ -13,8 +13,17 @@ namespace {
 
 __device__ __forceinline__ int refl1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
+// one pixel's four channels of a forward input: a 16-byte load (VEC: pixel pitch a multiple of 4 floats, 16-byte aligned base) or four
+// dword loads (a channel slice of a wider buffer at any pitch and channel offset).  The arithmetic behind it is the same: both
+// forms give the same bits, and a slice keeps the stencil kernel instead of the 128x32 matrix tile.
+template <bool VEC>
+__device__ __forceinline__ float4 c1_load4(const float* p) {
+  if constexpr (VEC) return *reinterpret_cast<const float4*>(p);
+  else return make_float4(p[0], p[1], p[2], p[3]);
+}
+
 // LP = lanes per pixel = C/4 (16, 32 or 64)
-template <int LP>
+template <int LP, bool VEC>
 __global__ __launch_bounds__(256) void c1_fwd_kernel(const float* x, int ldx, int B, int H, int W, const float* wp /*[9][C]*/,
                                                      const float* bias, int reflect, int act, float* y, int ldy) {
   constexpr int PPB = 256 / LP;                  // pixels per block pass
@@ -39,7 +48,7 @@ __global__ __launch_bounds__(256) void c1_fwd_kernel(const float* x, int ldx, in
         int wi = wq + kw - 1; bool ok = okh;
         if (reflect) wi = refl1(wi, W); else ok = ok && (unsigned)wi < (unsigned)W;
         if (ok) {
-          const float4 v = *reinterpret_cast<const float4*>(x + ((b * H + hi) * W + wi) * ldx + 4 * lane_c);
+          const float4 v = c1_load4<VEC>(x + ((b * H + hi) * W + wi) * ldx + 4 * lane_c);
           const float4 ww = w[kh * 3 + kw];
           acc += v.x * ww.x + v.y * ww.y + v.z * ww.z + v.w * ww.w;
         }
@@ -192,7 +201,7 @@ __device__ __forceinline__ Strip strip_decode(int sid, int nstrips, int nsr, int
   return t;
 }
 
-template <int LP>
+template <int LP, bool VEC>
 __global__ __launch_bounds__(256) void c1s_fwd_kernel(const float* x, int ldx, int B, int H, int W, const float* wp /*[9][C]*/,
                                                       const float* bias, int reflect, int act, float* y, int ldy) {
   constexpr int G = 256 / LP;
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(256) void c1s_fwd_kernel(const float* x, int ldx, i
         int wi = st.w0 - 1 + j; bool ok = okh;
         if (reflect) wi = refl1(wi, W); else ok = ok && (unsigned)wi < (unsigned)W;
         v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) v[j] = *reinterpret_cast<const float4*>(rp + (size_t)wi * ldx);
+        if (ok) v[j] = c1_load4<VEC>(rp + (size_t)wi * ldx);
       }
 #pragma unroll
       for (int j = 0; j < CS + 2; ++j)
@@ -464,6 +473,8 @@ inline int c1_blocks(long npix, int ppb) { long nb = (npix + ppb - 1) / ppb; ret
 }  // namespace
 
 bool segsde_c1_supported(int C, int ldx) { return (C == 64 || C == 128 || C == 256) && (ldx % 4 == 0); }
+// the forward kernels read their input at any pixel pitch and base alignment (c1_load4)
+bool segsde_c1_forward_supported(int C) { return C == 64 || C == 128 || C == 256; }
 
 size_t segsde_c1_wgrad_workspace(int C) { return (size_t)1024 * 9 * C * sizeof(float); }
 
@@ -480,16 +491,26 @@ inline bool c1_strips(int B, int H, int W) { return W % CS == 0 && (long)B * H *
     else hipLaunchKernelGGL((KERNEL<64>), grid, dim3(256), smem, ST(stream), __VA_ARGS__);          \
   } while (0)
 
+#define C1_DISPATCH_FWD(KERNEL, VEC, grid, ...)                                                         \
+  do {                                                                                                  \
+    if (C == 64) hipLaunchKernelGGL((KERNEL<16, VEC>), grid, dim3(256), 0, ST(stream), __VA_ARGS__);       \
+    else if (C == 128) hipLaunchKernelGGL((KERNEL<32, VEC>), grid, dim3(256), 0, ST(stream), __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<64, VEC>), grid, dim3(256), 0, ST(stream), __VA_ARGS__);               \
+  } while (0)
+
 int segsde_c1_forward(const float* x, int ldx, int B, int H, int W, int C, const float* wpack, const float* bias, int reflect,
                       int act, float* y, int ldy, void* stream) {
+  const bool vec = ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   if (c1_strips(B, H, W)) {
     const dim3 grid(c1s_blocks(B, H, W, 256 / (C / 4)));
-    C1_DISPATCH(c1s_fwd_kernel, grid, 0, x, ldx, B, H, W, wpack, bias, reflect, act, y, ldy);
+    if (vec) C1_DISPATCH_FWD(c1s_fwd_kernel, true, grid, x, ldx, B, H, W, wpack, bias, reflect, act, y, ldy);
+    else C1_DISPATCH_FWD(c1s_fwd_kernel, false, grid, x, ldx, B, H, W, wpack, bias, reflect, act, y, ldy);
     SEGSDE_CHECK_LAUNCH();
     return 0;
   }
   const dim3 grid(c1_blocks((long)B * H * W, 256 / (C / 4)));
-  C1_DISPATCH(c1_fwd_kernel, grid, 0, x, ldx, B, H, W, wpack, bias, reflect, act, y, ldy);
+  if (vec) C1_DISPATCH_FWD(c1_fwd_kernel, true, grid, x, ldx, B, H, W, wpack, bias, reflect, act, y, ldy);
+  else C1_DISPATCH_FWD(c1_fwd_kernel, false, grid, x, ldx, B, H, W, wpack, bias, reflect, act, y, ldy);
   SEGSDE_CHECK_LAUNCH();
   return 0;
 }

@@ -852,7 +852,10 @@ def conv_dgrad(g, dy, wdpack, w_oihw, in_hw, need0=True, need1=True, accumulate_
         # round 5: the skip-source gradient on the one-kernel Winograd route (flipped pack's columns [C0, C0 + C1), border kernel on
         # the forward pack's same channels); the folded call below then computes the upsampled source's gradient only
         w1 = None
-        if dx1f is not None and isinstance(wino, _KnPack) and wfpack is not None and routes.dgrad2 and (Ho, Wo) == (H, W):
+        # (a gradient slice off a 16-byte boundary: the border kernel would decline it AFTER the zero-padded launch wrote dx1 -- asked
+        # first, as on the single-source route above; such a slice stays on the folded route)
+        if (dx1f is not None and isinstance(wino, _KnPack) and wfpack is not None and routes.dgrad2 and (Ho, Wo) == (H, W)
+                and _reflect_borders2_ok(dy, H, W, g.C1, Cout)):
             r = winograd_fused("conv_dgrad", dy, wino, tag="%d+0->%d k3 s1 d1 %dx%d refl skip-of-%d+%d" % (Cout, g.C1, H, W, g.C0, g.C1),
                                accumulate_into=acc1, adjoint=wfpack, cols=(g.C0, g.C1))
             if r is not None:
