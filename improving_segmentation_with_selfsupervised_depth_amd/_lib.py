@@ -205,6 +205,11 @@ _SIGS = {
     "segsde_berhu_workspace": (c_size_t, [c_long]),
     "segsde_berhu_forward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, c_double, P, P, P, c_size_t, P]),
     "segsde_berhu_backward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "segsde_depth_hist_workspace": (c_size_t, [c_int, c_long]),
+    "segsde_depth_hist_thresholds": (c_int, [P, c_int, c_long, c_int, P, P, P, P, c_size_t, P]),
+    "segsde_depth_threshold_mask_batch": (c_int, [P, c_int, c_long, P, c_long, P, P]),
+    "segsde_class_presence": (c_int, [P, c_int, c_long, P, P]),
+    "segsde_class_mask_batch": (c_int, [P, c_int, c_long, P, P, P]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -1733,6 +1733,91 @@ def class_mask(pred, classes):
     return mask
 
 
+# the whole batch per launch (csrc/mixmask.hip): the "depth", "depthhist" and "class" masks of Trainer.generate_mix_mask
+MIX_CLASS_SLOTS = 256         # class ids -1 .. 254 in slots 0 .. 255
+MIX_HIST_BINS = 100           # np.histogram(..., bins=100), train.py:619
+
+
+def upload(host, device):
+    """one host -> device copy the host does not wait for (through pinned memory on a ROCm device)"""
+    if device.type == "cuda":
+        return host.pin_memory().to(device, non_blocking=True)
+    return host.to(device)
+
+
+def _mix_batch(t, dtype, name):
+    """-> (dense tensor, B, pixels per image) of a [B, ...] batch"""
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise TypeError("%s must be a %s tensor, got %s" % (name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() < 2 or t.numel() < 1:
+        raise ValueError("%s must be a non-empty batch [B, ...], got %s" % (name, tuple(t.shape)))
+    B, HW = int(t.shape[0]), t[0].numel()
+    if HW >= 2 ** 31:
+        raise ValueError("%s: %d pixels per image, the kernels index fewer than 2^31" % (name, HW))
+    return t.contiguous(), B, HW
+
+
+def _mix_per_image(t, dtype, like, shape, name):
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise TypeError("%s must be a %s tensor, got %s" % (name, dtype, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.device != like.device:
+        raise ValueError("%s is on %s, the batch on %s" % (name, t.device, like.device))
+    if tuple(t.shape) != shape:
+        raise ValueError("%s must have shape %s (one row per image), got %s" % (name, shape, tuple(t.shape)))
+    return t
+
+
+def depth_hist_thresholds(depths, u, apply_log=True, want_counts=False):
+    """The thresholds of the "depthhist" mix mask (train.py:616-631) for a batch: depths float32 [B, ...], u float32 [B] on the same
+    device (the reference's ``torch.rand(1)`` per image) -> (table float32 [B,4] = {min_depth, max_depth, threshold, found} per
+    image, counts int32 [B,100] or None).  The histogram is np.histogram(log(1 + depth), bins=100, density=True) restated in fp32
+    (segsde_depth_hist_thresholds in include/segsde_hip.h); ``apply_log=False`` takes the histogram of the values as they are.
+    An image without a bin for max_depth (found = 0) takes max_depth of the image before it, image 0 its top edge.  Three
+    launches, nothing returns to the host."""
+    d, B, HW = _mix_batch(depths, torch.float32, "depths")
+    u = _mix_per_image(u, torch.float32, d, (B,), "u").contiguous()
+    table = torch.empty((B, 4), dtype=torch.float32, device=d.device)
+    counts = torch.empty((B, MIX_HIST_BINS), dtype=torch.int32, device=d.device) if want_counts else None
+    L = _lib.lib()
+    nb = L.segsde_depth_hist_workspace(B, HW)
+    ws_ = _ws(nb, d)
+    check(L.segsde_depth_hist_thresholds(_p(d), B, HW, int(bool(apply_log)), _p(u), _p(table), _p(counts), _p(ws_), nb, _stream(d)),
+          "depth_hist_thresholds")
+    return table, counts
+
+
+def depth_threshold_mask_batch(depths, thr):
+    """mask[b] = (depths[b] >= thr[b]).float() for a batch in one launch: depths float32 [B, ...], thr float32 [B] on the same
+    device, possibly a strided view (column 2 of depth_hist_thresholds' table is read in place) -> float32, depths' shape."""
+    d, B, HW = _mix_batch(depths, torch.float32, "depths")
+    thr = _mix_per_image(thr, torch.float32, d, (B,), "thr")
+    stride = int(thr.stride(0)) if B > 1 else 0
+    if stride < 0:
+        thr, stride = thr.contiguous(), 1
+    mask = torch.empty_like(d)
+    check(_lib.lib().segsde_depth_threshold_mask_batch(_p(d), B, HW, _p(thr), stride, _p(mask), _stream(d)),
+          "depth_threshold_mask_batch")
+    return mask
+
+
+def class_presence(pred):
+    """pred int64 [B, ...] -> int32 [B,256]: pixels of image b with class id k in [b, k + 1], ids -1 .. 254 (others: nowhere)"""
+    p, B, HW = _mix_batch(pred, torch.int64, "pred")
+    counts = torch.empty((B, MIX_CLASS_SLOTS), dtype=torch.int32, device=p.device)
+    check(_lib.lib().segsde_class_presence(_p(p), B, HW, _p(counts), _stream(p)), "class_presence")
+    return counts
+
+
+def class_mask_batch(pred, selected):
+    """mask[b] = selected[b, pred[b] + 1] (0 for ids outside -1 .. 254): pred int64 [B, ...], selected uint8 [B,256] on the same
+    device -> int64, pred's shape.  transformmasks.generate_class_mask of every image against its own class list, one launch."""
+    p, B, HW = _mix_batch(pred, torch.int64, "pred")
+    selected = _mix_per_image(selected, torch.uint8, p, (B, MIX_CLASS_SLOTS), "selected").contiguous()
+    mask = torch.empty_like(p)
+    check(_lib.lib().segsde_class_mask_batch(_p(p), B, HW, _p(selected), _p(mask), _stream(p)), "class_mask_batch")
+    return mask
+
+
 # ----------------------------------------------------------------------------------------------
 # trainer-side callers (SURVEY.md 8(f) rows 1 and 3)
 # ----------------------------------------------------------------------------------------------

@@ -105,20 +105,17 @@ def normalize_online_depth(disp):
 
 
 def generate_mix_mask(mode, argmax_u_w, unlabeled_imgs, depths, depthcomp_margin=0.03, depthcomp_foreground_threshold=0.0):
-    """Trainer.generate_mix_mask (train.py:572-642): "class" / "depthcomp" / "depth" / None on the HIP mask kernels
-    ("depthhist" is CPU numpy histogram code in the reference and is not part of the path)."""
+    """Trainer.generate_mix_mask (train.py:572-642): "class" / "depthcomp" / "depth" / "depthhist" / None on the HIP mask
+    kernels, each a fixed number of launches for the whole batch.  Only "class" copies anything to the host: the B x 256 class
+    counters its numpy draw needs, once per call.  The random streams are the reference's: numpy's global generator for
+    "class", one host ``torch.rand(1)`` per image, in image order, for "depth" and "depthhist"."""
     from .loader import transformmasks
     B = unlabeled_imgs.shape[0]
     dev = unlabeled_imgs.device
     if mode == "class":
-        masks = []
-        for i in range(B):
-            classes = torch.unique(argmax_u_w[i])
-            classes = classes[classes != 250]
-            n = classes.shape[0]
-            pick = torch.as_tensor(np.random.choice(n, int((n - n % 2) / 2), replace=False), dtype=torch.int64, device=dev)
-            masks.append(transformmasks.generate_class_mask(argmax_u_w[i], classes[pick]).unsqueeze(0))
-        return torch.cat(masks)
+        return transformmasks.generate_class_mix_masks(argmax_u_w[:B])
+    if mode == "depthhist":
+        return transformmasks.generate_depthhist_mask(depths[:B])
     if mode == "depthcomp":
         ft = depthcomp_foreground_threshold
         if isinstance(ft, (tuple, list)):
@@ -128,11 +125,8 @@ def generate_mix_mask(mode, argmax_u_w, unlabeled_imgs, depths, depthcomp_margin
             ft = torch.rand(B, device=dev) * (ft_u - ft_l) + ft_l
         return transformmasks.generate_depthcomp_mask(depths, depthcomp_margin, ft)
     if mode == "depth":
-        masks = []
-        for i in range(B):
-            thr = torch.rand(1) * (0.4 - 0.1) + 0.1
-            masks.append(transformmasks.generate_depth_mask(depths[i], thr))
-        return torch.cat(masks)
+        thr = torch.cat([torch.rand(1) * (0.4 - 0.1) + 0.1 for _ in range(B)])
+        return transformmasks.generate_depth_masks(depths[:B], thr)
     if mode is None:
         return torch.ones((B,) + tuple(unlabeled_imgs.shape[2:]), device=dev)
     raise NotImplementedError(f"Unknown mix_mask {mode}")

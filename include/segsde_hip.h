@@ -830,6 +830,39 @@ int segsde_berhu_forward(const float* input, const float* target, const float* m
 int segsde_berhu_backward(const float* input, const float* target, const float* mask, long n, int H, int W, int keep_rows,
                           int apply_log, const float* state, const float* gscale, float* dinput, void* stream);
 
+/* ---- Mix masks for a whole batch (Trainer.generate_mix_mask, train.py:573-584 "class", 605-615 "depth", 616-636 "depthhist"),
+ * csrc/mixmask.hip.  depth: dense float32 [B][HW]; pred: dense int64 [B][HW]; 1 <= HW < 2^31; B <= 65535.
+ * segsde_depth_hist_thresholds: per image i, in order (train.py:616-631):
+ *   x = depth (apply_log = 0) or logf(1.0f + depth) (apply_log = 1);
+ *   counts, edges = np.histogram(x, bins=100) as numpy 2.2 computes it for float32 data: lo = min x, hi = max x (lo - 0.5, hi + 0.5
+ *   when they are equal); edges[k] = float32(k) * ((hi - lo) / 100) + lo in fp32, product and sum rounded separately, edges[100] = hi;
+ *   x counts in the bin k with edges[k] <= x < edges[k + 1], the last bin closed on the right;
+ *   density[k] = counts[k] / double(edges[k + 1] - edges[k]) / HW, the edge difference in fp32 first;
+ *   max_depth = edges[k + 1] of the highest k <= 98 with density[k] > 1.5; min_depth = edges[k] of the first k at which the running
+ *   sum of the densities (ascending k, double) divided by their total exceeds 0.4;
+ *   thr = u[i] * (max_depth - min_depth) + min_depth in fp32, product and sum rounded separately;
+ *   table[i] = {min_depth, max_depth, thr, found}.  found = 1 when a bin qualified for max_depth.  Otherwise found = 0 and max_depth
+ *   is that of image i - 1 of the same call, for image 0 its own edges[100] (the reference keeps the stale value of the previous
+ *   image without saying so, and fails on the first image).
+ * counts: uint32 [B][100] or null (the counters then live in the workspace).  u: device float32 [B].  Three launches (block minima
+ * and maxima; histogram in block-private LDS counters flushed with integer atomics; one block for the scans), no host
+ * synchronisation, no float atomics: two calls give identical bits.  NaN and depth <= -1 with apply_log: unspecified.
+ * segsde_depth_threshold_mask_batch: mask[b][p] = depth[b][p] >= thr[b * thr_stride] ? 1 : 0 (float32), thr in device memory --
+ * thr = table + 2, thr_stride = 4 reads the thresholds where the call above left them.  One launch.
+ * segsde_class_presence: counts[b][id + 1] = number of pixels of image b with that id, ids -1 .. 254 (slot 0 is the -1 that
+ * segsde_pseudo_label writes for ignore_index = -1); other ids are counted nowhere.  counts (uint32 [B][256]) is zeroed by the call.
+ * segsde_class_mask_batch: mask[b][p] = selected[b][pred[b][p] + 1] (uint8 [B][256]) for ids -1 .. 254, else 0 -- the
+ * generate_class_mask (transformmasks.py:27-30) of every image of the batch against its own class list, one launch.
+ * Checks, in this order, before any launch: SEGSDE_ERR_NULL; SEGSDE_ERR_SHAPE (B < 1, HW < 1, HW >= 2^31, thr_stride < 0);
+ * SEGSDE_ERR_UNSUPPORTED for B > 65535; SEGSDE_ERR_WORKSPACE (fewer than the workspace function's bytes; 0 for a refused shape);
+ * SEGSDE_ERR_UNSUPPORTED for a pointer that is not aligned to its element type. */
+size_t segsde_depth_hist_workspace(int B, long HW);
+int segsde_depth_hist_thresholds(const float* depth, int B, long HW, int apply_log, const float* u, float* table, unsigned* counts,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int segsde_depth_threshold_mask_batch(const float* depth, int B, long HW, const float* thr, long thr_stride, float* mask, void* stream);
+int segsde_class_presence(const int64_t* pred, int B, long HW, unsigned* counts, void* stream);
+int segsde_class_mask_batch(const int64_t* pred, int B, long HW, const unsigned char* selected, int64_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
