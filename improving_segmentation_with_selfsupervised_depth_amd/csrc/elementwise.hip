@@ -278,7 +278,8 @@ __device__ __forceinline__ float bn_dz_remask(float dy, float xh, float gamma, f
   if (act != SEGSDE_ACT_RELU) return dy;
   float t = xh;
   if (affine) t = t * gamma + beta;
-  return t > 0.f ? dy : 0.f;
+  // the product bn_dz forms from the saved output (dy * 0, not a selected +0): -0, NaN and Inf in dy propagate as in that mode
+  return dy * (t > 0.f ? 1.f : 0.f);
 }
 
 // MASK ("bitmask"): the ReLU derivative comes from the packed bits bn_apply_kernel<4, true> wrote (y points at the words; ReLU,
