@@ -1412,6 +1412,7 @@ extern "C" int segsde_smoothness_forward(const float* disp, const float* img, in
 extern "C" int segsde_smoothness_backward(const float* disp, const float* img, const float* mean_disp, int B, int h, int w,
                                           float scale, float* gdisp, void* ws_, size_t ws_bytes, void* stream) {
   if (!disp || !img || !mean_disp || !gdisp || !ws_) return SEGSDE_ERR_NULL;
+  if (B <= 0 || h < 2 || w < 2) return SEGSDE_ERR_SHAPE;    // as the forward: sx / sy below divide by (w - 1) and (h - 1)
   if (ws_bytes < segsde_smoothness_workspace(B, h, w)) return SEGSDE_ERR_WORKSPACE;
   const long HW = (long)h * w;
   const int nb = plane_blocks(HW);

@@ -572,6 +572,26 @@ def _f32(t, name="tensor"):
     return t
 
 
+# Operand lifetime: ``_p`` hands the C call a bare address, so the tensor behind it must be referenced by a local name of the
+# wrapper until ``check`` / ``_timed`` has returned.  Taking the address of ``t.contiguous()`` inline does not do that: for a
+# strided ``t`` the copy is released as soon as ``_p`` returns, before the launch, and a second copy of the same size may be given
+# its block.  The wrappers therefore bind ``x = _cf32(x)`` / ``x = _c(x)`` on the lines before the call (a contiguous operand is
+# returned as it is: no copy on the training path), and buffers a kernel writes or accumulates into go through ``_dense``.
+def _c(t):
+    return None if t is None else t.contiguous()
+
+
+def _cf32(t, name="tensor"):
+    return _f32(t, name).contiguous()
+
+
+def _dense(t, name):
+    """an operand read or written in place through its address: never with the wrong strides"""
+    if t is not None and not t.is_contiguous():
+        raise ValueError("%s must be contiguous, got strides %s for shape %s" % (name, t.stride(), tuple(t.shape)))
+    return t
+
+
 def nhwc_ld(t):
     """pixel pitch of an NHWC tensor (validates that it is a dense-row channel slice)"""
     B, H, W, C = t.shape
@@ -1298,7 +1318,8 @@ def scale_channels(x, scale):
     """x: NHWC [B,H,W,C]; scale [B,C] -> x * scale[b, c] (nn.Dropout2d mask application and its adjoint)"""
     B, Hh, W, C = x.shape
     y = torch.empty((B, Hh, W, C), dtype=torch.float32, device=x.device)
-    check(_lib.lib().segsde_scale_channels(_p(_f32(x)), nhwc_ld(x), B, Hh * W, C, _p(_f32(scale.contiguous())), _p(y), C,
+    scale = _cf32(scale, "scale")
+    check(_lib.lib().segsde_scale_channels(_p(_f32(x)), nhwc_ld(x), B, Hh * W, C, _p(scale), _p(y), C,
                                            _stream(x)), "scale_channels")
     return y
 
@@ -1422,10 +1443,12 @@ def pose_matrix(axisangle, translation, invert):
 
 
 def pose_matrix_backward(axisangle, translation, dM, invert):
+    _dense(_f32(axisangle, "axisangle"), "axisangle"), _dense(_f32(translation, "translation"), "translation")
+    dM = _cf32(dM, "dM")
     B = axisangle.shape[0]
     stride = axisangle.stride(0) if B > 1 else axisangle[0].numel()
     daa, dtr = torch.zeros_like(axisangle), torch.zeros_like(translation)
-    check(_lib.lib().segsde_pose_matrix_backward(_p(axisangle), _p(translation), _p(_f32(dM.contiguous())), B, int(stride),
+    check(_lib.lib().segsde_pose_matrix_backward(_p(axisangle), _p(translation), _p(dM), B, int(stride),
                                                  int(invert), _p(daa), _p(dtr), _stream(axisangle)), "pose_bwd")
     return daa, dtr
 
@@ -1439,8 +1462,9 @@ def warp_forward(disp, inv_K, K, T, src, min_depth, max_depth, want_grid=False, 
     color = torch.empty((B, 3, H, W), dtype=torch.float32, device=src.device)
     grid = torch.empty((B, H, W, 2), dtype=torch.float32, device=src.device) if want_grid else None
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=src.device) if want_depth else None
-    _timed('hbm_warp_fwd', 4.0 * B * (hs * ws + (3 + 3 + (2 if want_grid else 0) + (1 if want_depth else 0)) * H * W), src, lambda: check(_lib.lib().segsde_warp_forward(_p(_f32(disp.contiguous())), hs, ws, _p(_f32(inv_K.contiguous())),
-                                         _p(_f32(K.contiguous())), _p(_f32(T.contiguous())), _p(_f32(src.contiguous())),
+    disp, inv_K, K, T, src = _cf32(disp, "disp"), _cf32(inv_K, "inv_K"), _cf32(K, "K"), _cf32(T, "T"), _cf32(src, "src")
+    _timed('hbm_warp_fwd', 4.0 * B * (hs * ws + (3 + 3 + (2 if want_grid else 0) + (1 if want_depth else 0)) * H * W), src, lambda: check(_lib.lib().segsde_warp_forward(_p(disp), hs, ws, _p(inv_K),
+                                         _p(K), _p(T), _p(src),
                                          B, H, W, float(min_depth), float(max_depth), _p(color), _p(grid), _p(depth),
                                          _stream(src)), "warp_fwd"))
     return color, grid, depth
@@ -1453,8 +1477,10 @@ def warp_backward(gcolor, disp, inv_K, K, T, src, min_depth, max_depth, g_disp_u
     L = _lib.lib()
     nb = L.segsde_warp_backward_workspace(B, H, W)
     ws_ = _ws(nb, src)
-    check(L.segsde_warp_backward(_p(_f32(gcolor.contiguous())), _p(disp.contiguous()), hs, ws, _p(inv_K.contiguous()),
-                                 _p(K.contiguous()), _p(T.contiguous()), _p(src.contiguous()), B, H, W, float(min_depth),
+    gcolor, disp, inv_K, K, T, src = _cf32(gcolor, "gcolor"), _c(disp), _c(inv_K), _c(K), _c(T), _c(src)
+    _dense(g_disp_up, "g_disp_up"), _dense(gT, "gT")
+    check(L.segsde_warp_backward(_p(gcolor), _p(disp), hs, ws, _p(inv_K),
+                                 _p(K), _p(T), _p(src), B, H, W, float(min_depth),
                                  float(max_depth), _p(g_disp_up), _p(gT), _p(ws_), nb, _stream(src)), "warp_bwd")
 
 
@@ -1462,7 +1488,8 @@ def reprojection_error(pred, target, no_ssim, out_plane):
     """out_plane: a [B,H,W] view (channel of a [B,n,H,W] tensor)"""
     B, _, H, W = pred.shape
     assert out_plane.stride(2) == 1 and out_plane.stride(1) == W
-    check(_lib.lib().segsde_reprojection_error_forward(_p(_f32(pred.contiguous())), _p(_f32(target.contiguous())), B, H, W,
+    pred, target = _cf32(pred, "pred"), _cf32(target, "target")
+    check(_lib.lib().segsde_reprojection_error_forward(_p(pred), _p(target), B, H, W,
                                                        int(no_ssim), _p(out_plane), int(out_plane.stride(0)) if B > 1 else H * W,
                                                        _stream(pred)), "reproj_err_fwd")
 
@@ -1472,8 +1499,11 @@ def reprojection_error_backward(pred, target, gerr_plane, no_ssim):
     L = _lib.lib()
     nb = 0 if no_ssim else L.segsde_reprojection_error_backward_workspace(B, H, W)
     ws_ = _ws(nb, pred) if nb else None
+    pred, target = _c(pred), _c(target)
+    if gerr_plane.stride(2) != 1 or gerr_plane.stride(1) != W:
+        raise ValueError("gerr_plane must be a [B,H,W] view with dense rows, got strides %s" % (gerr_plane.stride(),))
     gpred = torch.empty_like(pred)
-    check(L.segsde_reprojection_error_backward(_p(pred.contiguous()), _p(target.contiguous()), _p(gerr_plane),
+    check(L.segsde_reprojection_error_backward(_p(pred), _p(target), _p(gerr_plane),
                                                int(gerr_plane.stride(0)) if B > 1 else H * W, B, H, W, int(no_ssim),
                                                _p(gpred), _p(ws_), nb, _stream(pred)), "reproj_err_bwd")
     return gpred
@@ -1483,8 +1513,9 @@ def photometric_identity(src0, src1, target, no_ssim):
     """err(src_f, target), f = 0, 1 -> [B,2,H,W] (the auto-mask's identity terms, the same for every scale)"""
     B, _, Hh, W = target.shape
     ident = torch.empty((B, 2, Hh, W), dtype=torch.float32, device=target.device)
-    _timed('hbm_photometric_identity', 4.0 * B * Hh * W * (9 + 2), target, lambda: check(_lib.lib().segsde_photometric_identity(_p(_f32(src0.contiguous())), _p(_f32(src1.contiguous())),
-                                                 _p(_f32(target.contiguous())), B, Hh, W, int(no_ssim), _p(ident),
+    src0, src1, target = _cf32(src0, "src0"), _cf32(src1, "src1"), _cf32(target, "target")
+    _timed('hbm_photometric_identity', 4.0 * B * Hh * W * (9 + 2), target, lambda: check(_lib.lib().segsde_photometric_identity(_p(src0), _p(src1),
+                                                 _p(target), B, Hh, W, int(no_ssim), _p(ident),
                                                  _stream(target)), "photometric_identity"))
     return ident
 
@@ -1498,7 +1529,9 @@ def photometric_forward(pred0, pred1, target, ident, noise, no_ssim, avg, want_s
     out = torch.empty(1, dtype=torch.float32, device=target.device)
     nb = L.segsde_photometric_workspace(B, Hh, W)
     ws_ = _ws(nb, target)
-    _timed('hbm_photometric_fwd', B * Hh * W * (4.0 * (9 + (2 if ident is not None else 0) + (2 if noise is not None else 0) + (1 if isel is not None else 0)) + 1.0), target, lambda: check(L.segsde_photometric_forward(_p(_f32(pred0.contiguous())), _p(_f32(pred1.contiguous())), _p(_f32(target.contiguous())),
+    pred0, pred1, target = _cf32(pred0, "pred0"), _cf32(pred1, "pred1"), _cf32(target, "target")
+    ident, noise = _c(ident), _c(noise)
+    _timed('hbm_photometric_fwd', B * Hh * W * (4.0 * (9 + (2 if ident is not None else 0) + (2 if noise is not None else 0) + (1 if isel is not None else 0)) + 1.0), target, lambda: check(L.segsde_photometric_forward(_p(pred0), _p(pred1), _p(target),
                                        _p(ident), _p(noise), B, Hh, W, int(no_ssim), int(avg), _p(sel), _p(isel), _p(out),
                                        _p(ws_), nb, _stream(target)), "photometric_forward"))
     return out, sel, isel
@@ -1514,10 +1547,14 @@ def photometric_backward(pred0, pred1, target, sel, has_ident, disp, inv_K, K, T
     gup = torch.empty((B, Hh, W), dtype=torch.float32, device=target.device)
     nb = L.segsde_photometric_workspace(B, Hh, W)
     ws_ = _ws(nb, target)
-    _timed('hbm_photometric_bwd', B * (Hh * W * (4.0 * (9 + 6 + 1) + 1.0) + 4.0 * hs * ws), target, lambda: check(L.segsde_photometric_backward(_p(pred0.contiguous()), _p(pred1.contiguous()), _p(target.contiguous()), _p(sel),
-                                        2 if has_ident else 0, _p(disp.contiguous()), hs, ws, _p(inv_K.contiguous()),
-                                        _p(K.contiguous()), _p(T0.contiguous()), _p(T1.contiguous()), _p(src0.contiguous()),
-                                        _p(src1.contiguous()), B, Hh, W, float(min_depth), float(max_depth), int(no_ssim),
+    pred0, pred1, target, disp, src0, src1 = _c(pred0), _c(pred1), _c(target), _c(disp), _c(src0), _c(src1)
+    inv_K, K, T0, T1 = _c(inv_K), _c(K), _c(T0), _c(T1)
+    sel = _c(sel)
+    _dense(gT0, "gT0"), _dense(gT1, "gT1")
+    _timed('hbm_photometric_bwd', B * (Hh * W * (4.0 * (9 + 6 + 1) + 1.0) + 4.0 * hs * ws), target, lambda: check(L.segsde_photometric_backward(_p(pred0), _p(pred1), _p(target), _p(sel),
+                                        2 if has_ident else 0, _p(disp), hs, ws, _p(inv_K),
+                                        _p(K), _p(T0), _p(T1), _p(src0),
+                                        _p(src1), B, Hh, W, float(min_depth), float(max_depth), int(no_ssim),
                                         int(avg), float(scale), _p(weight), _p(gup), _p(gT0), _p(gT1), _p(ws_), nb,
                                         _stream(target)), "photometric_backward"))
     return gup
@@ -1531,7 +1568,8 @@ def automask_min(ident, noise, reproj, avg, want_selection=True):
     out = torch.empty(1, dtype=torch.float32, device=reproj.device)
     nb = L.segsde_automask_workspace(B, H, W)
     ws_ = _ws(nb, reproj)
-    check(L.segsde_automask_min_forward(_p(ident), _p(noise), _p(_f32(reproj)), nr, int(avg), B, H, W, _p(sel), _p(isel),
+    ident, noise, reproj = _c(ident), _c(noise), _cf32(reproj, "reproj")
+    check(L.segsde_automask_min_forward(_p(ident), _p(noise), _p(reproj), nr, int(avg), B, H, W, _p(sel), _p(isel),
                                         _p(out), _p(ws_), nb, _stream(reproj)), "automask_fwd")
     return out, sel, isel
 
@@ -1539,6 +1577,7 @@ def automask_min(ident, noise, reproj, avg, want_selection=True):
 def automask_min_backward(sel, has_ident, n_reproj, avg, scale):
     B, H, W = sel.shape
     g = torch.empty((B, n_reproj, H, W), dtype=torch.float32, device=sel.device)
+    sel = _c(sel)
     check(_lib.lib().segsde_automask_min_backward(_p(sel), 2 if has_ident else 0, n_reproj, int(avg), B, H, W, float(scale),
                                                   _p(g), _stream(sel)), "automask_bwd")
     return g
@@ -1551,7 +1590,8 @@ def smoothness_forward(disp, img):
     out = torch.empty(1, dtype=torch.float32, device=disp.device)
     nb = L.segsde_smoothness_workspace(B, h, w)
     ws_ = _ws(nb, disp)
-    _timed('hbm_smooth_fwd', 16.0 * B * h * w, disp, lambda: check(L.segsde_smoothness_forward(_p(_f32(disp.contiguous())), _p(_f32(img.contiguous())), B, h, w, _p(mean), _p(out),
+    disp, img = _cf32(disp, "disp"), _cf32(img, "img")
+    _timed('hbm_smooth_fwd', 16.0 * B * h * w, disp, lambda: check(L.segsde_smoothness_forward(_p(disp), _p(img), B, h, w, _p(mean), _p(out),
                                       _p(ws_), nb, _stream(disp)), "smooth_fwd"))
     return out, mean
 
@@ -1562,7 +1602,9 @@ def smoothness_backward(disp, img, mean, scale, gdisp):
     L = _lib.lib()
     nb = L.segsde_smoothness_workspace(B, h, w)
     ws_ = _ws(nb, disp)
-    _timed('hbm_smooth_bwd', 24.0 * B * h * w, disp, lambda: check(L.segsde_smoothness_backward(_p(disp.contiguous()), _p(img.contiguous()), _p(mean), B, h, w, float(scale),
+    disp, img, mean = _c(disp), _c(img), _c(mean)
+    _dense(gdisp, "gdisp")
+    _timed('hbm_smooth_bwd', 24.0 * B * h * w, disp, lambda: check(L.segsde_smoothness_backward(_p(disp), _p(img), _p(mean), B, h, w, float(scale),
                                        _p(gdisp), _p(ws_), nb, _stream(disp)), "smooth_bwd"))
 
 
@@ -1573,7 +1615,8 @@ def smooth_loss_forward(disp, img):
     out = torch.empty(1, dtype=torch.float32, device=disp.device)
     nb = L.segsde_smooth_loss_workspace(B, h, w)
     ws_ = _ws(nb, disp)
-    check(L.segsde_smooth_loss_forward(_p(_f32(disp.contiguous())), _p(_f32(img.contiguous())), B, h, w, _p(out), _p(ws_), nb,
+    disp, img = _cf32(disp, "disp"), _cf32(img, "img")
+    check(L.segsde_smooth_loss_forward(_p(disp), _p(img), B, h, w, _p(out), _p(ws_), nb,
                                        _stream(disp)), "smooth_loss_fwd")
     return out
 
@@ -1584,7 +1627,8 @@ def smooth_loss_backward(disp, img, scale):
     g = torch.zeros((B, 1, h, w), dtype=torch.float32, device=disp.device)
     nb = L.segsde_smooth_loss_workspace(B, h, w)
     ws_ = _ws(nb, disp)
-    check(L.segsde_smooth_loss_backward(_p(disp.contiguous()), _p(img.contiguous()), B, h, w, float(scale), _p(g), _p(ws_), nb,
+    disp, img = _c(disp), _c(img)
+    check(L.segsde_smooth_loss_backward(_p(disp), _p(img), B, h, w, float(scale), _p(g), _p(ws_), nb,
                                         _stream(disp)), "smooth_loss_bwd")
     return g
 
@@ -1594,7 +1638,8 @@ def ssim_map(x, y):
     B, C, Hh, W = x.shape
     assert tuple(y.shape) == tuple(x.shape)
     out = torch.empty((B, C, Hh, W), dtype=torch.float32, device=x.device)
-    check(_lib.lib().segsde_ssim_map_forward(_p(_f32(x.contiguous())), _p(_f32(y.contiguous())), B, C, Hh, W, _p(out),
+    x, y = _cf32(x, "x"), _cf32(y, "y")
+    check(_lib.lib().segsde_ssim_map_forward(_p(x), _p(y), B, C, Hh, W, _p(out),
                                              _stream(x)), "ssim_map_fwd")
     return out
 
@@ -1603,7 +1648,8 @@ def ssim_map_backward(x, y, gout, need_x=True, need_y=True):
     B, C, Hh, W = x.shape
     gx = torch.empty((B, C, Hh, W), dtype=torch.float32, device=x.device) if need_x else None
     gy = torch.empty((B, C, Hh, W), dtype=torch.float32, device=x.device) if need_y else None
-    check(_lib.lib().segsde_ssim_map_backward(_p(x.contiguous()), _p(y.contiguous()), _p(_f32(gout.contiguous())), B, C, Hh, W,
+    x, y, gout = _c(x), _c(y), _cf32(gout, "gout")
+    check(_lib.lib().segsde_ssim_map_backward(_p(x), _p(y), _p(gout), B, C, Hh, W,
                                               _p(gx), _p(gy), _stream(x)), "ssim_map_bwd")
     return gx, gy
 
@@ -1612,7 +1658,8 @@ def backproject_depth(depth, inv_K):
     """BackprojectDepth.forward (models/monodepth_layers.py:169-174): depth [B,1,H,W], inv_K [B,4,4] -> cam_points [B,4,H*W]"""
     B, _, Hh, W = depth.shape
     out = torch.empty((B, 4, Hh * W), dtype=torch.float32, device=depth.device)
-    check(_lib.lib().segsde_backproject_depth(_p(_f32(depth.contiguous())), _p(_f32(inv_K.contiguous())), B, Hh, W, _p(out),
+    depth, inv_K = _cf32(depth, "depth"), _cf32(inv_K, "inv_K")
+    check(_lib.lib().segsde_backproject_depth(_p(depth), _p(inv_K), B, Hh, W, _p(out),
                                               _stream(depth)), "backproject_depth")
     return out
 
@@ -1622,7 +1669,8 @@ def project3d(points, K, T, Hh, W, eps=1e-7):
     B = points.shape[0]
     assert tuple(points.shape) == (B, 4, Hh * W)
     out = torch.empty((B, Hh, W, 2), dtype=torch.float32, device=points.device)
-    check(_lib.lib().segsde_project3d(_p(_f32(points.contiguous())), _p(_f32(K.contiguous())), _p(_f32(T.contiguous())), B, Hh, W,
+    points, K, T = _cf32(points, "points"), _cf32(K, "K"), _cf32(T, "T")
+    check(_lib.lib().segsde_project3d(_p(points), _p(K), _p(T), B, Hh, W,
                                       float(eps), _p(out), _stream(points)), "project3d")
     return out
 
@@ -1631,7 +1679,8 @@ def backproject_depth_backward(g_cam, inv_K, Hh, W):
     """adjoint of backproject_depth w.r.t. the depth: g_cam [B,4,H*W] -> [B,1,H,W]"""
     B = g_cam.shape[0]
     out = torch.empty((B, 1, Hh, W), dtype=torch.float32, device=g_cam.device)
-    check(_lib.lib().segsde_backproject_depth_backward(_p(_f32(g_cam.contiguous())), _p(_f32(inv_K.contiguous())), B, Hh, W, _p(out),
+    g_cam, inv_K = _cf32(g_cam, "g_cam"), _cf32(inv_K, "inv_K")
+    check(_lib.lib().segsde_backproject_depth_backward(_p(g_cam), _p(inv_K), B, Hh, W, _p(out),
                                                        _stream(g_cam)), "backproject_depth_backward")
     return out
 
@@ -1644,8 +1693,9 @@ def project3d_backward(points, K, T, g_pix, Hh, W, eps=1e-7, need_points=True, n
     gT = torch.empty((B, 4, 4), dtype=torch.float32, device=points.device) if need_T else None
     nbytes = L.segsde_project3d_backward_workspace(B, Hh, W) if need_T else 0
     ws = _ws(nbytes, points) if need_T else None
-    check(L.segsde_project3d_backward(_p(_f32(points.contiguous())), _p(_f32(K.contiguous())), _p(_f32(T.contiguous())),
-                                      _p(_f32(g_pix.contiguous())), B, Hh, W, float(eps), _p(gp), _p(gT), _p(ws), nbytes,
+    points, K, T, g_pix = _cf32(points, "points"), _cf32(K, "K"), _cf32(T, "T"), _cf32(g_pix, "g_pix")
+    check(L.segsde_project3d_backward(_p(points), _p(K), _p(T),
+                                      _p(g_pix), B, Hh, W, float(eps), _p(gp), _p(gT), _p(ws), nbytes,
                                       _stream(points)), "project3d_backward")
     return gp, gT
 
@@ -1695,8 +1745,9 @@ def mix(mask, x):
 
 def mix_labels(mask, target):
     B, H, W = target.shape
+    mask, target = _c(mask), _c(target)
     out = torch.empty_like(target)
-    check(_lib.lib().segsde_mix_labels(_p(mask.contiguous()), _p(target.contiguous()), B, H, W, _p(out), _stream(target)),
+    check(_lib.lib().segsde_mix_labels(_p(mask), _p(target), B, H, W, _p(out), _stream(target)),
           "mix_labels")
     return out
 
@@ -1711,7 +1762,8 @@ def depthcomp_mask(depths, margin, fg_threshold):
         per = _f32(fg_threshold.reshape(-1)).to(depths.device).contiguous()
         if per.numel() != B:
             raise ValueError("one foreground threshold per image: got %d for a batch of %d" % (per.numel(), B))
-    check(_lib.lib().segsde_depthcomp_mask(_p(_f32(depths.contiguous())), B, HW, float(margin),
+    depths = _cf32(depths, "depths")
+    check(_lib.lib().segsde_depthcomp_mask(_p(depths), B, HW, float(margin),
                                            0.0 if per is not None else float(fg_threshold), _p(per), _p(mask),
                                            _stream(depths)), "depthcomp_mask")
     return mask
@@ -1868,7 +1920,8 @@ def color_jitter(x, params, order):
     assert C == 3 and tuple(params.shape) == (B, 4)
     y = torch.empty_like(x)
     arr = (ctypes.c_int * 4)(*[int(o) for o in order])
-    check(_lib.lib().segsde_color_jitter(_p(x), B, Hh * W, _p(_f32(params.contiguous())), arr, _p(y), _stream(x)), "color_jitter")
+    params = _cf32(params, "params")
+    check(_lib.lib().segsde_color_jitter(_p(x), B, Hh * W, _p(params), arr, _p(y), _stream(x)), "color_jitter")
     return y
 
 
@@ -1877,7 +1930,8 @@ def gaussian_blur(x, wy, wx):
     x = _f32(x).contiguous()
     B, C, Hh, W = x.shape
     tmp, y = torch.empty_like(x), torch.empty_like(x)
-    _timed('hbm_blur', 16.0 * x.numel(), x, lambda: check(_lib.lib().segsde_gaussian_blur(_p(x), B * C, Hh, W, _p(_f32(wy.contiguous())), wy.numel(), _p(_f32(wx.contiguous())),
+    wy, wx = _cf32(wy, "wy"), _cf32(wx, "wx")
+    _timed('hbm_blur', 16.0 * x.numel(), x, lambda: check(_lib.lib().segsde_gaussian_blur(_p(x), B * C, Hh, W, _p(wy), wy.numel(), _p(wx),
                                           wx.numel(), _p(tmp), _p(y), _stream(x)), "gaussian_blur"))
     return y
 
@@ -2016,7 +2070,8 @@ def batchprep_pyramid_level(src, coef, u8_out=None, f32_out=None):
     u8_out = _out_like(u8_out, lead + (Hd, Wd), torch.uint8, src, "u8_out")
     f32_out = _out_like(f32_out, lead + (Hd, Wd), torch.float32, src, "f32_out")
     planes = src.numel() // (Hs * Ws)
-    check(_lib.lib().segsde_batchprep_pyramid_level(_p(src), planes, Hs, Ws, _p(coef.contiguous()), Hd, Wd,
+    coef = _c(coef)
+    check(_lib.lib().segsde_batchprep_pyramid_level(_p(src), planes, Hs, Ws, _p(coef), Hd, Wd,
                                                     _p(u8_out), _p(f32_out), _stream(src)), "batchprep_pyramid_level")
     return u8_out, f32_out
 
@@ -2032,7 +2087,8 @@ def batchprep_labels(lbl, crop_xy, flip, ch, cw, lut, is_labeled=None, ignore_in
         raise TypeError("is_labeled must be uint8 [B]")
     out = torch.empty((B, ch, cw), dtype=torch.int64, device=lbl.device)
     onehot = torch.empty((B, n_classes, ch, cw), dtype=torch.int64, device=lbl.device) if want_onehot else None
-    check(_lib.lib().segsde_batchprep_labels(_p(lbl), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(lut.contiguous()),
+    lut = _c(lut)
+    check(_lib.lib().segsde_batchprep_labels(_p(lbl), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(lut),
                                              _p(is_labeled), int(ignore_index), int(n_classes), _p(out), _p(onehot), _stream(lbl)),
           "batchprep_labels")
     return out, onehot
@@ -2114,7 +2170,8 @@ def batchprep_labels_rgb(lbl, crop_xy, flip, ch, cw, colors, ignore_id=-1, is_la
         raise TypeError("is_labeled must be uint8 [B]")
     out = torch.empty((B, ch, cw), dtype=torch.int64, device=lbl.device)
     onehot = torch.empty((B, n_classes, ch, cw), dtype=torch.int64, device=lbl.device) if want_onehot else None
-    check(_lib.lib().segsde_batchprep_labels_rgb(_p(lbl), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(colors.contiguous()),
+    colors = _c(colors)
+    check(_lib.lib().segsde_batchprep_labels_rgb(_p(lbl), B, H, W, _p(crop_xy), _p(flip), int(ch), int(cw), _p(colors),
                                                  colors.numel(), int(ignore_id), _p(is_labeled), int(ignore_index), int(n_classes),
                                                  _p(out), _p(onehot), _stream(lbl)), "batchprep_labels_rgb")
     return out, onehot

@@ -213,8 +213,10 @@ def pil_resize(images, size, resample="antialias", tables=None, what="images"):
         return out
     upload = lambda rows: torch.from_numpy(np.array(rows, dtype=np.int64).reshape(-1, 8)).to(device)
     if resample == "nearest":
-        rows = [(s.data_ptr(), d.data_ptr(), tables.nearest(s.shape[0], height, device).data_ptr(),
-                 tables.nearest(s.shape[1], width, device).data_ptr(), s.shape[0], s.shape[1], 0, 0) for s, d in todo]
+        # the index tables stay referenced here until the launch has been issued, whatever cache ``tables`` keeps (or does not)
+        idx = [(tables.nearest(s.shape[0], height, device), tables.nearest(s.shape[1], width, device)) for s, _ in todo]
+        rows = [(s.data_ptr(), d.data_ptr(), ty.data_ptr(), tx.data_ptr(), s.shape[0], s.shape[1], 0, 0)
+                for (s, d), (ty, tx) in zip(todo, idx)]
         H.batchprep_resize_nearest(upload(rows), height, width, chan)
         return out
     for s, _ in todo:

@@ -77,6 +77,75 @@ def test_argument_validation_without_gpu():
     assert cdll.segsde_project3d_backward_workspace(0, 8, 8) == 0 and cdll.segsde_project3d_backward_workspace(2, 8, 8) > 0
     assert cdll.segsde_project3d_backward(fake, fake, fake, fake, 2, 8, 8, 1e-7, None, fake, None, 0, None) == -3               # d T needs the workspace
     assert cdll.segsde_backproject_depth_backward(None, None, 2, 8, 8, None, None) == -1
+    # the smoothness adjoint checks its shape like the forward (w == 1 would divide by zero in its normalisation)
+    assert cdll.segsde_smoothness_forward(fake, fake, 2, 8, 1, fake, fake, fake, 1 << 20, None) == -2
+    assert cdll.segsde_smoothness_backward(fake, fake, fake, 2, 8, 1, 1.0, fake, fake, 1 << 20, None) == -2
+    assert cdll.segsde_smoothness_backward(fake, fake, fake, 0, 8, 8, 1.0, fake, fake, 1 << 20, None) == -2
+    assert cdll.segsde_smoothness_backward(fake, fake, fake, 2, 1, 8, 1.0, fake, fake, 1 << 20, None) == -2
+
+
+def pointer_lifetime_violations(path):
+    """(line, text) of every place in a Python source where an address is taken of a tensor no name holds: the argument of
+    ``_p(...)`` / ``H._p(...)`` and the receiver of ``.data_ptr()`` may contain no call other than ``_f32(<name or attribute>)``
+    (which returns its argument).  ``_p(t.contiguous())`` is the defect this guards against: for a strided ``t`` the copy is
+    released when ``_p`` returns, before the kernel is launched.  Subscripts (views of a held buffer) are fine."""
+    import ast
+    src = open(path).read()
+    tree = ast.parse(src, path)
+
+    def plain(n):
+        return isinstance(n, ast.Name) or (isinstance(n, ast.Attribute) and plain(n.value))
+
+    def allowed(call):
+        f = call.func
+        is_f32 = (isinstance(f, ast.Name) and f.id == "_f32") or (isinstance(f, ast.Attribute) and f.attr == "_f32" and plain(f.value))
+        return is_f32 and len(call.args) >= 1 and plain(call.args[0]) and not call.keywords and \
+            all(isinstance(a, ast.Constant) for a in call.args[1:])
+
+    def temporaries(expr):
+        if isinstance(expr, ast.Subscript):                  # a view of what ``value`` holds; the index may compute what it likes
+            return temporaries(expr.value)
+        mine = [expr] if isinstance(expr, ast.Call) and not allowed(expr) else []
+        return mine + [c for child in ast.iter_child_nodes(expr) for c in temporaries(child)]
+
+    bad = []
+    for node in ast.walk(tree):
+        if not isinstance(node, ast.Call):
+            continue
+        f = node.func
+        if (isinstance(f, ast.Name) and f.id == "_p") or (isinstance(f, ast.Attribute) and f.attr == "_p"):
+            exprs = list(node.args)
+        elif isinstance(f, ast.Attribute) and f.attr == "data_ptr":
+            exprs = [f.value]
+        else:
+            continue
+        if any(temporaries(e) for e in exprs):
+            bad.append((node.lineno, ast.get_source_segment(src, node)))
+    return bad
+
+
+def package_sources():
+    return sorted(os.path.join(root, f) for root, _, files in os.walk(PKG) for f in files if f.endswith(".py"))
+
+
+def test_no_pointer_of_a_temporary():
+    """every tensor whose address goes to a kernel is held by a name of the caller (hipops' "Operand lifetime" note)"""
+    bad = {os.path.relpath(p, REPO): v for p in package_sources() for v in [pointer_lifetime_violations(p)] if v}
+    assert not bad, bad
+    # the textual form of the same defect
+    pat = re.compile(r"_p\((_f32\()?[^()]*\.(contiguous|float|to)\(")
+    hits = [(os.path.relpath(p, REPO), i + 1) for p in package_sources() for i, line in enumerate(open(p)) if pat.search(line)]
+    assert not hits, hits
+
+
+def test_pointer_guard_sees_the_defect(tmp_path):
+    """the guard flags the forms it exists for and passes the held ones"""
+    f = tmp_path / "sample.py"
+    f.write_text("def a(t):\n    return _p(_f32(t.contiguous()))\n"
+                 "def b(t):\n    return H._p(t.contiguous())\n"
+                 "def c(tables):\n    return tables.nearest(1, 2).data_ptr()\n"
+                 "def d(t, buf):\n    t = t.contiguous()\n    return _p(_f32(t)), _p(buf[1:]), H._p(H._f32(t)), buf[0].data_ptr(), _p(_f32(t, 'x'))\n")
+    assert [ln for ln, _ in pointer_lifetime_violations(str(f))] == [2, 4, 6]
 
 
 def test_product_never_imports_oracle_or_falls_back():
