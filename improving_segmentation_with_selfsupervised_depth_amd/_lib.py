@@ -100,6 +100,14 @@ _SIGS = {
     "segsde_bn_apply_mask": (c_int, [P, c_int, c_long, c_int, P, P, P, P, P, c_int, P, c_int, c_int, c_float, c_uint64, P, P]),
     "segsde_bn_backward_mask": (c_int, [P, c_int, P, P, c_int, c_long, c_int, P, P, P, c_int, c_float, c_int, P, P, P, c_int, P, c_int,
                                         P, c_size_t, P]),
+    "segsde_bn_sync_row_bytes": (c_size_t, [c_int]),
+    "segsde_bn_sync_stats_local": (c_int, [P, c_int, c_long, c_int, P, P, c_size_t, P]),
+    "segsde_bn_sync_stats_local_from_partials": (c_int, [P, c_long, c_long, c_int, P, P, c_size_t, P]),
+    "segsde_bn_sync_stats_global": (c_int, [P, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P]),
+    "segsde_bn_sync_backward_local": (c_int, [P, c_int, P, c_int, P, P, c_int, c_long, c_int, P, P, P, P, c_int, c_float, c_uint64,
+                                              c_int, P, P, P, P, c_size_t, P]),
+    "segsde_bn_sync_backward_global": (c_int, [P, c_int, P, c_int, P, P, c_int, c_long, c_int, P, P, P, P, c_int, c_float, c_uint64,
+                                               P, c_int, P, P, P, P, c_int, P, c_int, P]),
     "segsde_colsum_workspace": (c_size_t, [c_long, c_int]),
     "segsde_act_backward": (c_int, [P, c_int, P, c_int, c_long, c_int, c_int, P, c_int, P, P, c_size_t, P]),
     "segsde_colsum": (c_int, [P, c_int, c_long, c_int, P, P, c_size_t, P]),

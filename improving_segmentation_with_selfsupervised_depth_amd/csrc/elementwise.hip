@@ -343,10 +343,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int 
                                                            const float* invstd, const float* gamma, const float* beta,
                                                            int act, float drop_p, uint64_t seed, int batch_stats,
                                                            const float* dgamma, const float* dbeta, float* dx, int lddx,
-                                                           float* dres, int lddres, int cv_shift) {
+                                                           float* dres, int lddres, int cv_shift, const float* inv_count) {
   const int CV = C / VW;
   const long total = M * CV;
-  const float invM = 1.f / (float)M;
+  // inv_count (cross-replica BatchNorm, segsde_bn_sync_backward_global): 1 / (float)M_total as the statistics kernel left it on the
+  // device -- one uniform load per thread, nothing per element.  nullptr: the reciprocal of this launch's own row count, as ever
+  const float invM = inv_count ? inv_count[0] : 1.f / (float)M;
   static_assert(!MASK || VW == 4, "the mask words are read per channel quad");
   const bool remask = !MASK && y == nullptr;
   // per-channel parameters once per thread when every trip of the grid-stride loop meets the same channels (see bn_apply_kernel):
@@ -1069,11 +1071,11 @@ extern "C" int segsde_bn_backward(const float* dy, int lddy, const float* y, int
     if (v4)
       hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), dy, lddy, y, ldy, x,
                          ldx, M, C, mean, invstd, gamma, beta, act, drop_p, seed, batch_stats, (const float*)dgamma,
-                         (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C / 4));
+                         (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C / 4), (const float*)nullptr);
     else
       hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_blocks_cv(M * C, C)), dim3(256), 0, ST(stream), dy, lddy, y, ldy, x, ldx,
                          M, C, mean, invstd, gamma, beta, act, drop_p, seed, batch_stats, (const float*)dgamma,
-                         (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C));
+                         (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C), (const float*)nullptr);
     SEGSDE_CHECK_LAUNCH();
   }
   return 0;
@@ -1105,9 +1107,229 @@ extern "C" int segsde_bn_backward_mask(const float* dy, int lddy, const uint32_t
   if (dx || dres) {
     hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), dy, lddy,
                        bits, 0, x, ldx, M, C, mean, invstd, gamma, (const float*)nullptr, act, 0.f, (uint64_t)0, batch_stats,
-                       (const float*)dgamma, (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C / 4));
+                       (const float*)dgamma, (const float*)dbeta, dx, lddx, dres, lddres, pow2_shift(C / 4), (const float*)nullptr);
     SEGSDE_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------ cross-replica (synchronized) BatchNorm
+// The reductions above stop after their fold and leave one ROW of doubles per rank (layout: include/segsde_hip.h); the caller
+// all-gathers the rows; the global stages fold the W gathered rows in rank order, one thread per channel, and finish exactly as
+// the single-process kernels do.  No atomics, every order fixed: all ranks compute the same bits from the same gathered table,
+// and one gathered row (W = 1) reproduces segsde_bn_stats / segsde_bn_backward / segsde_bn_backward_mask bit for bit.
+namespace {
+__host__ __device__ inline long sync_row_len(int C) { return 2L * C + 2; }
+
+// block partials [nb][2][C] -> the row (and, for the backward pass, this rank's float dgamma / dbeta): combine_partials, the
+// fold of bn_stats_finalize_kernel and pair_finalize_kernel
+__global__ __launch_bounds__(256) void bn_sync_row_kernel(const double* part, int nb, long M, int C, double* row, float* out0,
+                                                          float* out1) {
+  SEGSDE_SMEM;
+  double* sh = reinterpret_cast<double*>(segsde_smem);
+  const int c = blockIdx.x * 16 + (threadIdx.x & 15), pl = threadIdx.x >> 4;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { row[2L * C] = (double)M; row[2L * C + 1] = 0.0; }
+  double a, b;
+  combine_partials(part, nb, C, c, pl, sh, a, b);
+  if (pl != 0 || c >= C) return;
+  row[c] = a; row[(long)C + c] = b;
+  if (out0) out0[c] = (float)a;
+  if (out1) out1[c] = (float)b;
+}
+
+// conv-epilogue partials [rows][2][C] of a few hundred rows -> the row in one launch: the fold of
+// bn_stats_from_partials_wide_kernel (4 channels x 64 row-lanes per block, lanes folded in lane order)
+__global__ __launch_bounds__(256) void bn_sync_row_wide_kernel(const double* part, long rows, long M, int C, double* row) {
+  SEGSDE_SMEM;
+  double* sh = reinterpret_cast<double*>(segsde_smem);   // [2][64][4]
+  const int cl = threadIdx.x & 3, rl = threadIdx.x >> 2, c = blockIdx.x * 4 + cl;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { row[2L * C] = (double)M; row[2L * C + 1] = 0.0; }
+  double a = 0.0, b = 0.0;
+  if (c < C)
+    for (long r = rl; r < rows; r += 64) { a += part[(r * 2) * C + c]; b += part[(r * 2 + 1) * C + c]; }
+  sh[rl * 4 + cl] = a; sh[256 + rl * 4 + cl] = b;
+  __syncthreads();
+  if (rl != 0 || c >= C) return;
+  double s = 0.0, q = 0.0;
+  for (int j = 0; j < 64; ++j) { s += sh[j * 4 + cl]; q += sh[256 + j * 4 + cl]; }
+  row[c] = s; row[(long)C + c] = q;
+}
+
+// W gathered rows -> statistics over all ranks' rows: the arithmetic of bn_stats_finalize_kernel with M_total read from the
+// gathered counts (integers below 2^53: their double sum is exact), so ranks may hold different numbers of rows
+__global__ __launch_bounds__(256) void bn_sync_stats_global_kernel(const double* rows, int W, int C, float eps, float momentum,
+                                                                   float* mean, float* invstd, float* running_mean,
+                                                                   float* running_var, int64_t* nbt, float* inv_count) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const long rl = sync_row_len(C);
+  double cnt = rows[2L * C];
+  for (int r = 1; r < W; ++r) cnt += rows[r * rl + 2L * C];
+  const long M = (long)cnt;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (nbt) nbt[0] += 1;
+    inv_count[0] = 1.f / (float)M;     // what bn_bwd_apply_kernel forms from its own M
+  }
+  if (c >= C) return;
+  double s = rows[c], q = rows[(long)C + c];
+  for (int r = 1; r < W; ++r) { s += rows[r * rl + c]; q += rows[r * rl + C + c]; }
+  const double mu = s / (double)M;
+  double var = q / (double)M - mu * mu;
+  if (var < 0.0) var = 0.0;
+  mean[c] = (float)mu;
+  invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mu;
+  if (running_var) {
+    const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
+  }
+}
+
+// W gathered backward rows -> float sums over all ranks (what pair_finalize_kernel rounds, from the wider sum)
+__global__ __launch_bounds__(256) void bn_sync_fold_kernel(const double* rows, int W, int C, float* out0, float* out1) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const long rl = sync_row_len(C);
+  double a = rows[c], b = rows[(long)C + c];
+  for (int r = 1; r < W; ++r) { a += rows[r * rl + c]; b += rows[r * rl + C + c]; }
+  out0[c] = (float)a;
+  out1[c] = (float)b;
+}
+inline bool al8p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+}  // namespace
+
+extern "C" size_t segsde_bn_sync_row_bytes(int C) { return C > 0 ? (size_t)sync_row_len(C) * sizeof(double) : 0; }
+
+extern "C" int segsde_bn_sync_stats_local(const float* x, int ldx, long M, int C, double* row, void* ws, size_t ws_bytes,
+                                          void* stream) {
+  if (!x || !row || !ws) return SEGSDE_ERR_NULL;
+  if (M <= 0 || C <= 0 || ldx < C) return SEGSDE_ERR_SHAPE;
+  if (ws_bytes < part_bytes(M, C)) return SEGSDE_ERR_WORKSPACE;
+  if (!al8p(row) || !al8p(ws)) return SEGSDE_ERR_UNSUPPORTED;
+  StatsOp op{x, ldx};
+  const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && al16p(x);      // segsde_bn_stats' choice: the same partials
+  if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream))) return e;
+  hipLaunchKernelGGL(bn_sync_row_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws, red_blocks(M), M, C,
+                     row, (float*)nullptr, (float*)nullptr);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_bn_sync_stats_local_from_partials(const double* partials, long rows, long M, int C, double* row, void* ws,
+                                                        size_t ws_bytes, void* stream) {
+  if (!partials || !row || !ws) return SEGSDE_ERR_NULL;
+  if (rows <= 0 || M <= 0 || C <= 0) return SEGSDE_ERR_SHAPE;
+  if (ws_bytes < segsde_bn_stats_from_partials_workspace(C)) return SEGSDE_ERR_WORKSPACE;
+  if (!al8p(row) || !al8p(ws) || !al8p(partials)) return SEGSDE_ERR_UNSUPPORTED;
+  // the three folds of segsde_bn_stats_from_partials, chosen by the same thresholds: one gathered row reproduces its sums
+  if (rows > 64 && rows <= partials_wide_max()) {
+    hipLaunchKernelGGL(bn_sync_row_wide_kernel, dim3((C + 3) / 4), dim3(256), 4096, ST(stream), partials, rows, M, C, row);
+    SEGSDE_CHECK_LAUNCH();
+    return 0;
+  }
+  const double* src = partials;
+  int nb = (int)rows;
+  if (rows > 64) {     // many tiles: 64 rows in the colreduce format first
+    nb = PARTIALS_NB;
+    hipLaunchKernelGGL(bn_partials_reduce_kernel, dim3(nb, (C + 63) / 64), dim3(256), 4096, ST(stream), partials, rows, C, nb,
+                       (double*)ws);
+    SEGSDE_CHECK_LAUNCH();
+    src = (const double*)ws;
+  }
+  hipLaunchKernelGGL(bn_sync_row_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), src, nb, M, C, row, (float*)nullptr,
+                     (float*)nullptr);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_bn_sync_stats_global(const double* rows, int W, int C, float* mean, float* invstd, float* running_mean,
+                                           float* running_var, float momentum, float eps, int64_t* num_batches_tracked,
+                                           float* inv_count, void* stream) {
+  if (!rows || !mean || !invstd || !inv_count) return SEGSDE_ERR_NULL;
+  if (W <= 0 || C <= 0) return SEGSDE_ERR_SHAPE;
+  if (!al8p(rows)) return SEGSDE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(bn_sync_stats_global_kernel, dim3((C + 255) / 256), dim3(256), 0, ST(stream), rows, W, C, eps, momentum, mean,
+                     invstd, running_mean, running_var, num_batches_tracked, inv_count);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+namespace {
+// the operand rules of segsde_bn_backward (mask == nullptr) and segsde_bn_backward_mask, shared by both backward stages:
+// 0 and *vec, or an error code
+int sync_bwd_operands(const float* dy, int lddy, const float* y, int ldy, const uint32_t* mask, const float* x, int ldx, long M, int C,
+                      const float* mean, const float* invstd, const float* gamma, const float* beta, int act, float drop_p,
+                      bool has_dres, bool* vec) {
+  if (!dy || !x || !mean || !invstd) return SEGSDE_ERR_NULL;
+  if (M <= 0 || C <= 0) return SEGSDE_ERR_SHAPE;
+  if (mask) {
+    if (act != SEGSDE_ACT_RELU || drop_p != 0.f) return SEGSDE_ERR_UNSUPPORTED;
+    *vec = (C % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) && al16p(x) && al16p(dy) && (!gamma || al16p(gamma)) && al16p(mean) &&
+           al16p(invstd) && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+    return *vec ? 0 : SEGSDE_ERR_UNSUPPORTED;     // channel quads only, as segsde_bn_backward_mask
+  }
+  if (!y && !(act == SEGSDE_ACT_NONE || (act == SEGSDE_ACT_RELU && drop_p <= 0.f && !has_dres && (!gamma || beta)))) return SEGSDE_ERR_NULL;
+  if (!y) ldy = ldx;
+  *vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (lddy % 4 == 0) && al16p(x) && (!y || al16p(y)) && al16p(dy) &&
+         (!gamma || (al16p(gamma) && (!beta || al16p(beta)))) && al16p(mean) && al16p(invstd);
+  return 0;
+}
+}  // namespace
+
+extern "C" int segsde_bn_sync_backward_local(const float* dy, int lddy, const float* y, int ldy, const uint32_t* mask, const float* x,
+                                             int ldx, long M, int C, const float* mean, const float* invstd, const float* gamma,
+                                             const float* beta, int act, float drop_p, uint64_t seed, int has_dres, float* dgamma,
+                                             float* dbeta, double* row, void* ws, size_t ws_bytes, void* stream) {
+  if (!dgamma || !dbeta || !row || !ws) return SEGSDE_ERR_NULL;
+  bool vec = false;
+  if (int e = sync_bwd_operands(dy, lddy, y, ldy, mask, x, ldx, M, C, mean, invstd, gamma, beta, act, drop_p, has_dres != 0, &vec))
+    return e;
+  if (ws_bytes < part_bytes(M, C)) return SEGSDE_ERR_WORKSPACE;
+  if (!al8p(row) || !al8p(ws)) return SEGSDE_ERR_UNSUPPORTED;
+  if (mask) {
+    BnBwdOpT<true> op{dy, lddy, reinterpret_cast<const float*>(mask), 0, x, ldx, mean, invstd, act, C, 0.f, 0, gamma, nullptr};
+    if (int e = launch_colreduce(op, M, C, (double*)ws, true, ST(stream))) return e;
+  } else {
+    BnBwdOp op{dy, lddy, y, y ? ldy : ldx, x, ldx, mean, invstd, act, C, drop_p, seed, gamma, beta};
+    if (int e = launch_colreduce(op, M, C, (double*)ws, vec, ST(stream))) return e;
+  }
+  hipLaunchKernelGGL(bn_sync_row_kernel, dim3((C + 15) / 16), dim3(256), 4096, ST(stream), (const double*)ws, red_blocks(M), M, C,
+                     row, dgamma, dbeta);
+  SEGSDE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int segsde_bn_sync_backward_global(const float* dy, int lddy, const float* y, int ldy, const uint32_t* mask, const float* x,
+                                              int ldx, long M, int C, const float* mean, const float* invstd, const float* gamma,
+                                              const float* beta, int act, float drop_p, uint64_t seed, const double* rows, int W,
+                                              const float* inv_count, float* dgamma_total, float* dbeta_total, float* dx, int lddx,
+                                              float* dres, int lddres, void* stream) {
+  if (!rows || !inv_count || !dgamma_total || !dbeta_total) return SEGSDE_ERR_NULL;
+  bool vec = false;
+  if (int e = sync_bwd_operands(dy, lddy, y, ldy, mask, x, ldx, M, C, mean, invstd, gamma, beta, act, drop_p, dres != nullptr, &vec))
+    return e;
+  if (W <= 0) return SEGSDE_ERR_SHAPE;
+  if (!al8p(rows)) return SEGSDE_ERR_UNSUPPORTED;
+  const bool v4 = vec && (!dx || ((lddx % 4 == 0) && al16p(dx))) && (!dres || ((lddres % 4 == 0) && al16p(dres))) &&
+                  al16p(dgamma_total) && al16p(dbeta_total);
+  if (mask && !v4) return SEGSDE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(bn_sync_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, ST(stream), rows, W, C, dgamma_total, dbeta_total);
+  SEGSDE_CHECK_LAUNCH();
+  if (!dx && !dres) return 0;
+  if (!y) ldy = ldx;
+  if (mask)
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<4, true>), dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), dy, lddy,
+                       reinterpret_cast<const float*>(mask), 0, x, ldx, M, C, mean, invstd, gamma, (const float*)nullptr, act, 0.f,
+                       (uint64_t)0, 1, (const float*)dgamma_total, (const float*)dbeta_total, dx, lddx, dres, lddres,
+                       pow2_shift(C / 4), inv_count);
+  else if (v4)
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_blocks_cv(M * C / 4, C / 4)), dim3(256), 0, ST(stream), dy, lddy, y, ldy, x, ldx,
+                       M, C, mean, invstd, gamma, beta, act, drop_p, seed, 1, (const float*)dgamma_total, (const float*)dbeta_total,
+                       dx, lddx, dres, lddres, pow2_shift(C / 4), inv_count);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_blocks_cv(M * C, C)), dim3(256), 0, ST(stream), dy, lddy, y, ldy, x, ldx, M, C,
+                       mean, invstd, gamma, beta, act, drop_p, seed, 1, (const float*)dgamma_total, (const float*)dbeta_total, dx,
+                       lddx, dres, lddres, pow2_shift(C), inv_count);
+  SEGSDE_CHECK_LAUNCH();
   return 0;
 }
 

@@ -36,7 +36,8 @@ Design notes
     that the old layout's collectives pair up on all ranks before the new layout's are issued;
   * a bucket member that NO rank produced a gradient for in this step keeps ``p.grad = None`` (as in the single-GPU
     run: momentum / weight-decay optimizers skip it), everything else receives the average;
-  * BatchNorm statistics stay per replica, exactly like N independent runs of the single-GPU reference.
+  * BatchNorm statistics stay per replica, exactly like N independent runs of the single-GPU reference, unless the model was
+    converted with ``convert_sync_batchnorm`` (cross-replica statistics: models.layers.SyncBatchNorm2d).
 """
 import contextlib
 import warnings
@@ -60,6 +61,48 @@ def seed_per_rank(base_seed, rank=None):
     np.random.seed(seed % (2 ** 31))
     random.seed(seed)
     return seed
+
+
+def convert_sync_batchnorm(module, process_group=None, only=None):
+    """Turn the ``models.layers.BatchNorm2d`` modules of a model into ``models.layers.SyncBatchNorm2d`` (training statistics over
+    all ranks of ``process_group``; None: the default group at call time), like ``nn.SyncBatchNorm.convert_sync_batchnorm``.
+    The conversion is IN PLACE: each module object changes its class and keeps its parameters, buffers, hooks and caches, so
+    ``state_dict()`` keys, parameter identities and ``named_parameters()`` order are unchanged, and optimizer param groups, EMA
+    tables, weight-pack and frozen-BatchNorm-fold caches built before or after the call stay valid; a checkpoint saved before
+    loads strictly after.  Converting twice is a no-op.  Returns ``module``.
+
+    only: an iterable of sub-model names -- keys of ``module.models`` (JointSegmentationMonodepth: "encoder", "depth",
+    "segmentation", ...) or, for other modules, names of direct children -- to convert just those.  Default: everything except the
+    pose networks (``models`` keys starting with "pose": their loss couples the frames of one sample, not the batch); name them
+    to convert them too.  An EMA teacher is a model of its own and is converted only if the caller passes it: it runs under
+    ``no_grad`` in train mode, so a converted teacher issues its forward collectives in every step and must be called on every
+    rank alike.
+
+    Call it once, before building the optimizer and the GradAllReducer.  Gradient convention (torch.nn.SyncBatchNorm's): the
+    gradient with respect to a BatchNorm input is that of the SUM of the ranks' losses; dgamma / dbeta are this rank's sums and
+    are averaged by the reducer like every other gradient.  Every rank must run the same BatchNorms in the same order in each
+    forward and backward (trainer.train_step does); the collectives cannot be captured in a hipGraph."""
+    from torch import nn
+
+    from .models.layers import BatchNorm2d, SyncBatchNorm2d
+    subs = getattr(module, "models", None)
+    if only is not None:
+        table = subs if isinstance(subs, nn.ModuleDict) else dict(module.named_children())
+        names = list(only)
+        missing = [n for n in names if n not in table]
+        if missing:
+            raise KeyError("convert_sync_batchnorm: no sub-model named %s (have %s)" % (missing, sorted(table.keys())))
+        roots = [table[n] for n in names]
+    elif isinstance(subs, nn.ModuleDict):
+        roots = [m for n, m in subs.items() if not n.startswith("pose")]
+    else:
+        roots = [module]
+    for root in roots:
+        for m in root.modules():
+            if isinstance(m, BatchNorm2d) and not isinstance(m, SyncBatchNorm2d):
+                m.__class__ = SyncBatchNorm2d
+                m.process_group = process_group
+    return module
 
 
 # Gradient destinations: parameter storage address -> [view of the parameter's bucket slice, step id of the claim, bucket, index].  The

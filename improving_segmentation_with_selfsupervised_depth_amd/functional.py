@@ -370,15 +370,36 @@ class ActGradFn(Function):
         return dz, None, None
 
 
+def _gather_rows(row, group):
+    """the exchange of the cross-replica BatchNorm: every rank's row, in rank order, as one [W, len] table (the same table on
+    every rank, so every rank derives the same bits from it)"""
+    import torch.distributed as dist
+    W = dist.get_world_size(group)
+    rows = torch.empty(W * row.numel(), dtype=row.dtype, device=row.device)      # (flat: the form every backend takes)
+    dist.all_gather_into_tensor(rows, row, group=group)
+    return rows.view(W, row.numel())
+
+
 class BNActFn(Function):
-    """y = dropout(act(BN(x) + residual)); training=True uses batch statistics and updates the running buffers."""
+    """y = dropout(act(BN(x) + residual)); training=True uses batch statistics and updates the running buffers.
+    group (a torch.distributed process group; None: this process alone, today's path): in training the statistics run over the
+    rows of all ranks of the group -- local sums, one all-gather of a row of doubles, a fold in rank order (hipops.bn_sync_*) --
+    and the backward pass exchanges its two channel sums the same way: dx is the gradient of the SUM of the ranks' losses,
+    dgamma / dbeta stay this rank's sums (GradAllReducer averages them like every other gradient).  Eval mode issues no
+    collective.  Every rank must run the same BatchNorms in the same order, forward and backward."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, training, momentum, eps, act, drop_p, seed,
-                partials=None, grad_box=None, nbt=None):
+                partials=None, grad_box=None, nbt=None, group=None):
         ctx.grad_box = grad_box
         x = _c(x)
-        if training and partials is not None:
+        ctx.sync = None
+        if training and group is not None:
+            rows = _gather_rows(H.bn_sync_stats_local(x, partials), group)
+            mean, invstd, inv_count = H.bn_sync_stats_global(rows, x.shape[-1], running_mean, running_var, momentum, eps,
+                                                             update_running=running_mean is not None, num_batches_tracked=nbt)
+            ctx.sync = (group, inv_count)
+        elif training and partials is not None:
             # the producing convolution already summed x and x^2 per tile in its epilogue
             mean, invstd = H.bn_stats_from_partials(partials, x.numel() // x.shape[-1], running_mean, running_var, momentum,
                                                     eps, update_running=running_mean is not None, num_batches_tracked=nbt)
@@ -411,11 +432,26 @@ class BNActFn(Function):
         want_g = gamma is not None and ctx.needs_input_grad[1]
         bp = ctx.beta_param
         note = {}
-        dx, dres, dgamma, dbeta = H.bn_backward(_c(dy), y, x, mean, invstd, gamma, act, drop_p, seed, batch_stats=training,
-                                                need_dx=ctx.needs_input_grad[0],
-                                                need_dres=has_res and ctx.needs_input_grad[3], beta=beta, mask=mask, note=note,
-                                                dgamma_out=_grad_dest(gamma) if want_g else None,
-                                                dbeta_out=_grad_dest(bp) if (want_g and bp is not None and ctx.needs_input_grad[2]) else None)
+        dgamma_out = _grad_dest(gamma) if want_g else None
+        dbeta_out = _grad_dest(bp) if (want_g and bp is not None and ctx.needs_input_grad[2]) else None
+        need_dres = has_res and ctx.needs_input_grad[3]
+        if ctx.sync is not None:
+            group, inv_count = ctx.sync
+            dy = _c(dy)
+            # the collective is issued whatever this rank needs of the result: the other ranks wait for this rank's row
+            row, dgamma, dbeta, used = H.bn_sync_backward_local(dy, y, x, mean, invstd, gamma, act, drop_p, seed, need_dres=need_dres,
+                                                                beta=beta, dgamma_out=dgamma_out, dbeta_out=dbeta_out, mask=mask)
+            rows = _gather_rows(row, group)
+            dx = dres = None
+            if ctx.needs_input_grad[0] or need_dres:
+                dx, dres = H.bn_sync_backward_global(rows, inv_count, dy, y, x, mean, invstd, gamma, act, drop_p, seed,
+                                                     need_dx=ctx.needs_input_grad[0], need_dres=need_dres, beta=beta,
+                                                     mask=mask if used else None)
+            note["mask_used"] = used
+        else:
+            dx, dres, dgamma, dbeta = H.bn_backward(_c(dy), y, x, mean, invstd, gamma, act, drop_p, seed, batch_stats=training,
+                                                    need_dx=ctx.needs_input_grad[0], need_dres=need_dres, beta=beta, mask=mask,
+                                                    note=note, dgamma_out=dgamma_out, dbeta_out=dbeta_out)
         ctx.beta_param = None
         if ctx.mask_route:
             # counted from what the kernel did: shapes without a mask flavour ran this backward from the saved output
@@ -424,7 +460,7 @@ class BNActFn(Function):
             dgamma = dbeta = None
         if ctx.grad_box is not None and dres is not None:
             ctx.grad_box["g"] = dres         # the block's first conv may add its data-gradient onto this tensor
-        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class SplitFn(Function):

@@ -1160,6 +1160,113 @@ def bn_backward(dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, b
     return dx, dres, dgamma, dbeta
 
 
+# ---- cross-replica BatchNorm: the four stages of segsde_bn_sync_* (the all-gather between them is the caller's: functional.BNActFn)
+_BN_SYNC_ROW = {}             # channel count -> doubles per exchange row (a pure function of C)
+
+
+def bn_sync_row_len(C):
+    """doubles in one exchange row: C sums, C second sums, the row count, padding to 16 bytes (include/segsde_hip.h)"""
+    n = _BN_SYNC_ROW.get(C)
+    if n is None:
+        n = _BN_SYNC_ROW[C] = _lib.lib().segsde_bn_sync_row_bytes(C) // 8
+    return n
+
+
+def bn_sync_stats_local(x, partials=None):
+    """this rank's statistics row (float64 [bn_sync_row_len(C)]) from x, or from the partial sums [rows][2][C] a
+    conv_forward(want_stats=True) launch left behind (x then only gives the row count)"""
+    M, C, ld = _rows(x)
+    L = _lib.lib()
+    row = torch.empty(bn_sync_row_len(C), dtype=torch.float64, device=x.device)
+    if partials is not None:
+        nb = _BN_PARTIALS_WS.get(C)
+        if nb is None:
+            nb = _BN_PARTIALS_WS[C] = L.segsde_bn_stats_from_partials_workspace(C)
+        ws = _ws(nb, x)
+        check(L.segsde_bn_sync_stats_local_from_partials(_p(partials), partials.shape[0], M, C, _p(row), _p(ws), nb, _stream(x)),
+              "bn_sync_stats_local_from_partials")
+        return row
+    nb = L.segsde_bn_stats_workspace(M, C)
+    ws = _ws(nb, x)
+    _timed('hbm_bn_stats', 4.0 * M * C, x, lambda: check(L.segsde_bn_sync_stats_local(_p(_f32(x)), ld, M, C, _p(row), _p(ws), nb, _stream(x)),
+                                                         "bn_sync_stats_local"))
+    return row
+
+
+def bn_sync_stats_global(rows, C, running_mean, running_var, momentum, eps, update_running=True, num_batches_tracked=None):
+    """rows: the gathered table, float64 [W, bn_sync_row_len(C)] in rank order -> (mean, invstd, inv_count); inv_count is the
+    device float 1 / (float)M_total that bn_sync_backward_global reads"""
+    rows = _dense(rows, "rows")
+    W = rows.shape[0]
+    if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != bn_sync_row_len(C):
+        raise ValueError("rows must be float64 [W, %d], got %s %s" % (bn_sync_row_len(C), rows.dtype, tuple(rows.shape)))
+    mi = torch.empty((3, C), dtype=torch.float32, device=rows.device)     # one allocation; inv_count is mi[2, :1]
+    mean, invstd, inv_count = mi[0], mi[1], mi[2, :1]
+    check(_lib.lib().segsde_bn_sync_stats_global(_p(rows), W, C, _p(mean), _p(invstd), _p(running_mean if update_running else None),
+                                                 _p(running_var if update_running else None), float(momentum), float(eps),
+                                                 _p(num_batches_tracked), _p(inv_count), _stream(rows)), "bn_sync_stats_global")
+    return mean, invstd, inv_count
+
+
+def bn_sync_backward_local(dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, need_dres=False, beta=None,
+                           dgamma_out=None, dbeta_out=None, mask=None):
+    """the reductions of bn_backward, stopped after the fold -> (row, dgamma, dbeta, mask_used): this rank's float dgamma / dbeta
+    (written into dgamma_out / dbeta_out where given) and the same sums as the float64 exchange row.  y=None: the remask mode;
+    mask: the packed ReLU bits, read in place of y where segsde_bn_backward_mask would take the call (else y is)."""
+    M, C, ldx = _rows(x)
+    L = _lib.lib()
+
+    def _dst(t):
+        ok = t is not None and tuple(t.shape) == (C,) and t.is_contiguous() and t.dtype == torch.float32
+        return t if ok else torch.empty(C, dtype=torch.float32, device=x.device)
+    dgamma, dbeta = _dst(dgamma_out), _dst(dbeta_out)
+    row = torch.empty(bn_sync_row_len(C), dtype=torch.float64, device=x.device)
+    nb = L.segsde_bn_backward_workspace(M, C)
+    ws = _ws(nb, x)
+    lddy = _rows(dy)[2]
+    if mask is not None:
+        if _taken("bn_sync_backward_local_mask", 'hbm_bn_backward', 8.125 * M * C, x,
+                  lambda: L.segsde_bn_sync_backward_local(_p(_f32(dy)), lddy, _p(None), 0, _p(mask), _p(x), ldx, M, C, _p(mean), _p(invstd),
+                                                          _p(gamma), _p(None), ACT[act], float(drop_p), 0, int(need_dres), _p(dgamma),
+                                                          _p(dbeta), _p(row), _p(ws), nb, _stream(x)), may_decline=y is not None):
+            return row, dgamma, dbeta, True
+    ldy = _rows(y)[2] if y is not None else ldx
+    _timed('hbm_bn_backward', (8.0 + (4.0 if y is not None else 0.0)) * M * C, x, lambda: check(L.segsde_bn_sync_backward_local(
+        _p(_f32(dy)), lddy, _p(y), ldy, _p(None), _p(x), ldx, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), ACT[act], float(drop_p),
+        int(seed), int(need_dres), _p(dgamma), _p(dbeta), _p(row), _p(ws), nb, _stream(x)), "bn_sync_backward_local"))
+    return row, dgamma, dbeta, False
+
+
+def bn_sync_backward_global(rows, inv_count, dy, y, x, mean, invstd, gamma, act="none", drop_p=0.0, seed=0, need_dx=True,
+                            need_dres=False, beta=None, mask=None):
+    """rows: the gathered backward rows, float64 [W, bn_sync_row_len(C)] -> (dx, dres): the apply pass of bn_backward with the
+    sums over all ranks and 1 / M_total (inv_count, from bn_sync_stats_global).  mask: pass it exactly when the local stage read it."""
+    M, C, ldx = _rows(x)
+    rows = _dense(rows, "rows")
+    if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != bn_sync_row_len(C):
+        raise ValueError("rows must be float64 [W, %d], got %s %s" % (bn_sync_row_len(C), rows.dtype, tuple(rows.shape)))
+    W = rows.shape[0]
+    L = _lib.lib()
+    tot = torch.empty((2, C + (-C) % 4), dtype=torch.float32, device=x.device)      # both totals 16-byte aligned
+    dg, db = tot[0], tot[1]
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dx else None
+    dres = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dres else None
+    lddy = _rows(dy)[2]
+    nbytes = ((8.0 if (need_dx or mask is None and y is None) else 4.0) + (4.0 if need_dx else 0.0) + (4.0 if need_dres else 0.0)) * M * C
+    if mask is not None:
+        if _taken("bn_sync_backward_global_mask", 'hbm_bn_backward', nbytes + 0.125 * M * C, x,
+                  lambda: L.segsde_bn_sync_backward_global(_p(_f32(dy)), lddy, _p(None), 0, _p(mask), _p(x), ldx, M, C, _p(mean),
+                                                           _p(invstd), _p(gamma), _p(None), ACT[act], float(drop_p), 0, _p(rows), W,
+                                                           _p(inv_count), _p(dg), _p(db), _p(dx), C, _p(dres), C, _stream(x)),
+                  may_decline=y is not None):
+            return dx, dres
+    ldy = _rows(y)[2] if y is not None else ldx
+    _timed('hbm_bn_backward', nbytes + (4.0 if y is not None else 0.0) * M * C, x, lambda: check(L.segsde_bn_sync_backward_global(
+        _p(_f32(dy)), lddy, _p(y), ldy, _p(None), _p(x), ldx, M, C, _p(mean), _p(invstd), _p(gamma), _p(beta), ACT[act], float(drop_p),
+        int(seed), _p(rows), W, _p(inv_count), _p(dg), _p(db), _p(dx), C, _p(dres), C, _stream(x)), "bn_sync_backward_global"))
+    return dx, dres
+
+
 def act_backward(dy, y, act, need_dbias=False, need_dz=True):
     M, C, ldy = _rows(y)
     L = _lib.lib()

@@ -184,6 +184,8 @@ class BatchNorm2d(nn.BatchNorm2d):
     """nn.BatchNorm2d state; ``forward(x_nhwc, residual=None, act="none", drop_p=0.0)`` fuses the residual add,
     the activation and (for ASPP.project) the dropout into the normalisation pass."""
 
+    _synchronized = False      # SyncBatchNorm2d: training statistics over all ranks of a process group
+
     def forward(self, x, residual=None, act="none", drop_p=0.0, grad_box=None):
         training = self.training or (self.running_mean is None)
         # num_batches_tracked is incremented by the statistics finalize kernel (no launch of its own)
@@ -213,8 +215,38 @@ class BatchNorm2d(nn.BatchNorm2d):
                 producer._stats_wanted = True
         if training:
             Fn.fusion("bn_stats_from_conv_epilogue", partials is not None)
+            group = self._group() if self._synchronized else None
+            if group is not None:
+                return Fn.BNActFn.apply(x, self.weight, self.bias, residual, self.running_mean, self.running_var, training,
+                                        momentum, self.eps, act, drop_p, seed, partials, grad_box, nbt, group)
         return Fn.BNActFn.apply(x, self.weight, self.bias, residual, self.running_mean, self.running_var, training,
                                 momentum, self.eps, act, drop_p, seed, partials, grad_box, nbt)
+
+
+class SyncBatchNorm2d(BatchNorm2d):
+    """BatchNorm2d whose TRAINING statistics run over the rows of every rank of a torch.distributed process group (cross-replica /
+    synchronized BatchNorm, as torch.nn.SyncBatchNorm), with everything BatchNorm2d fuses kept: residual add, activation, dropout,
+    the 1-bit ReLU mask, statistics from the convolution epilogue.  Same ``forward``, parameters, buffers and ``state_dict`` keys.
+    ``process_group`` None: the default group, looked up at call time.  Outside an initialised process group, or in a default group
+    of one rank, it is BatchNorm2d; so it is in eval mode (also ``freeze_backbone_bn`` and the frozen-BatchNorm folding): no
+    collective.  Per training forward one all-gather of 2 C + 2 doubles, per backward another (Fn.BNActFn); every rank must call the
+    same modules in the same order, and a module that runs under ``no_grad`` in train mode (an EMA teacher) still issues its forward
+    collective, so it must do so on every rank alike.  Not capturable in a hipGraph.  ddp.convert_sync_batchnorm converts a model."""
+
+    _synchronized = True
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, process_group=None):
+        super().__init__(num_features, eps, momentum, affine, track_running_stats)
+        self.process_group = process_group
+
+    def _group(self):
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return None
+        pg = self.__dict__.get("process_group")
+        if pg is None:
+            return dist.group.WORLD if dist.get_world_size() > 1 else None
+        return pg
 
 
 def _tensor_key(t):

@@ -256,6 +256,48 @@ int segsde_bn_backward_mask(const float* dy, int lddy, const uint32_t* mask, con
                             const float* mean, const float* invstd, const float* gamma, int act, float drop_p,
                             int batch_stats, float* dgamma, float* dbeta, float* dx, int lddx, float* dres, int lddres,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Cross-replica (synchronized) BatchNorm for data-parallel training: the reductions above cut in two, with a seam where the
+ * caller's collective sits.  A LOCAL stage reduces this rank's rows to one ROW of doubles, the caller all-gathers the rows of the
+ * W ranks (rank order), a GLOBAL stage folds the gathered rows in rank order and finishes.  No atomics, every order fixed: all
+ * ranks get the same bits from the same table, and with W = 1 and statistics taken from x the results equal those of
+ * segsde_bn_stats / segsde_bn_backward / segsde_bn_backward_mask bit for bit.
+ *   ROW layout, segsde_bn_sync_row_bytes(C) = (2 C + 2) * 8 bytes (a multiple of 16), 8-byte aligned:
+ *     doubles [0, C)      forward: sum x        backward: sum dz * xhat   (this rank's rows, per channel)
+ *     doubles [C, 2 C)    forward: sum x^2      backward: sum dz
+ *     double  2 C         this rank's row count M (an integer value)
+ *     double  2 C + 1     0 (padding to 16 bytes)
+ *   rows: W such rows back to back, as all_gather_into_tensor leaves them.
+ * segsde_bn_sync_stats_local: the row from x (workspace: segsde_bn_stats_workspace(M, C)).
+ * segsde_bn_sync_stats_local_from_partials: the row from the [rows][2][C] partials of a convolution epilogue (workspace:
+ *   segsde_bn_stats_from_partials_workspace(C)), folded as segsde_bn_stats_from_partials folds them (a single gathered row gives
+ *   that entry's bits); the same sums as the x source in another order, so the two sources agree to rounding only.
+ * segsde_bn_sync_stats_global: mean / invstd / running buffers / num_batches_tracked as segsde_bn_stats computes them, over
+ *   M_total = the sum of the gathered counts, which is read on the device (ranks may hold different numbers of rows; M_total == 1
+ *   keeps the biased variance in the running update); inv_count[0] = 1 / (float)M_total, a device float for the backward pass.
+ * segsde_bn_sync_backward_local: the reduction of segsde_bn_backward (mask == NULL; y == NULL: its remask mode) or of
+ *   segsde_bn_backward_mask (mask != NULL, y ignored), with their operand rules and error codes (has_dres: whether the global
+ *   stage will write dres -- the remask mode does not allow it); writes this rank's float dgamma / dbeta (the parameter
+ *   gradients: local sums, averaged over ranks like every other gradient) and the row (workspace: segsde_bn_backward_workspace).
+ * segsde_bn_sync_backward_global: folds the W gathered rows to dgamma_total / dbeta_total (float [C] scratch, written) and
+ *   runs the apply pass of segsde_bn_backward with those totals and inv_count in place of 1 / (float)M: dx is the gradient of the
+ *   SUM of the ranks' losses with respect to this rank's x; dres = dz.  dx and dres nullable. */
+size_t segsde_bn_sync_row_bytes(int C);
+int segsde_bn_sync_stats_local(const float* x, int ldx, long M, int C, double* row, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int segsde_bn_sync_stats_local_from_partials(const double* partials, long rows, long M, int C, double* row, void* workspace,
+                                             size_t workspace_bytes, void* stream);
+int segsde_bn_sync_stats_global(const double* rows, int W, int C, float* mean, float* invstd, float* running_mean,
+                                float* running_var, float momentum, float eps, int64_t* num_batches_tracked, float* inv_count,
+                                void* stream);
+int segsde_bn_sync_backward_local(const float* dy, int lddy, const float* y, int ldy, const uint32_t* mask, const float* x, int ldx,
+                                  long M, int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                  int act, float drop_p, uint64_t seed, int has_dres, float* dgamma, float* dbeta, double* row,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int segsde_bn_sync_backward_global(const float* dy, int lddy, const float* y, int ldy, const uint32_t* mask, const float* x, int ldx,
+                                   long M, int C, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                   int act, float drop_p, uint64_t seed, const double* rows, int W, const float* inv_count,
+                                   float* dgamma_total, float* dbeta_total, float* dx, int lddx, float* dres, int lddres,
+                                   void* stream);
 /* dz = dy * act'(y) (ELU / ReLU / sigmoid via the saved output, as the reference's in-place ops do);
  * dbias[c] = sum_rows dz (nullable).  Replaces autograd of nn.ELU / nn.ReLU / torch.sigmoid + conv bias grad. */
 size_t segsde_colsum_workspace(long M, int C);
