@@ -262,10 +262,13 @@ def build_state_dict(model_cfg, n_classes, seed=0, randomize_bn=False, zero_atte
 # --------------------------------------------------------------------------
 class Ctx:
     """train: BatchNorm uses batch statistics and updates running stats in ``sd``;
-    dropout: apply nn.Dropout/Dropout2d layers (fresh torch RNG) -- parity runs keep it off."""
+    dropout: apply nn.Dropout/Dropout2d layers (fresh torch RNG unless ``drop_masks`` is given);
+    drop_masks: optional callable (site, shape_nchw, p, two_d) -> keep tensor (bool or 0/1, broadcastable to shape_nchw) that
+    decides every dropped element; ``site`` is the state-dict path of the nn.Dropout / nn.Dropout2d module in the reference's
+    layout (``...decoder.N.project.3``, ``...head.0``, ``...head.4``, ``...decoder.N.block.3``)."""
 
-    def __init__(self, sd, train=True, dropout=False):
-        self.sd, self.train, self.dropout = sd, train, dropout
+    def __init__(self, sd, train=True, dropout=False, drop_masks=None):
+        self.sd, self.train, self.dropout, self.drop_masks = sd, train, dropout, drop_masks
 
 
 def _conv(c, key, x, stride=1, padding=0, dilation=1):
@@ -280,9 +283,12 @@ def _bn(c, key, x):
                         sd[key + ".bias"], training=c.train, momentum=0.1, eps=1e-5)
 
 
-def _drop(c, x, p, two_d=False):
+def _drop(c, x, p, two_d=False, site=None):
     if not (c.dropout and c.train) or p <= 0:
         return x
+    if c.drop_masks is not None:
+        keep = torch.as_tensor(c.drop_masks(site, tuple(x.shape), p, two_d)).to(x.dtype)
+        return x * keep / (1 - p)
     return F.dropout2d(x, p, True) if two_d else F.dropout(x, p, True)
 
 
@@ -323,7 +329,7 @@ def _convblock(c, q, e, x, dropout):
     x = _refl_conv3(c, q + "block.0.conv", x)
     if e["bn"]:
         x = _bn(c, q + "block.1", x)
-    return _drop(c, F.elu(x), dropout, two_d=True)
+    return _drop(c, F.elu(x), dropout, two_d=True, site=q + "block.3")
 
 
 def _aspp(c, q, e, x):
@@ -338,7 +344,7 @@ def _aspp(c, q, e, x):
         g = F.relu(_bn(c, q + "convs.%d.2" % k, _conv(c, q + "convs.%d.1" % k, g)))
         outs.append(F.interpolate(g, size=x.shape[-2:], mode="bilinear", align_corners=False))
     y = F.relu(_bn(c, q + "project.1", _conv(c, q + "project.0", torch.cat(outs, 1))))
-    return _drop(c, y, 0.5)
+    return _drop(c, y, 0.5, site=q + "project.3")
 
 
 def decoder_forward(c, p, plan, feats, x=None, exec_layer=None, enable_disparity=True):
@@ -388,10 +394,10 @@ def jsd_forward(c, p, plan, feats, seg_args):
     for layer in layers:
         y = _conv(c, p + "project.seg%d.0" % layer, _layer(feats, dec, layer))
         stacked.append(F.interpolate(y, size=last_size, mode="bilinear", align_corners=False))
-    y = _drop(c, torch.cat(stacked, 1), seg_args.get("layer_dropout", 0))
+    y = _drop(c, torch.cat(stacked, 1), seg_args.get("layer_dropout", 0), site=p + "head.0")
     if seg_args.get("head_inter", True):
         y = F.relu(_bn(c, p + "head.2", _conv(c, p + "head.1", y, 1, 1)))
-        y = _drop(c, y, seg_args.get("head_dropout", 0.1))
+        y = _drop(c, y, seg_args.get("head_dropout", 0.1), site=p + "head.4")
         y = _conv(c, p + "head.5", y)
     else:
         y = _conv(c, p + "head.2", y)
@@ -406,7 +412,8 @@ def _self_attention(c, q, x):
 
 
 def pad_forward(c, p, plan, feats, seg_args):
-    """joint_segmentation_depth_decoder.py:134-184."""
+    """joint_segmentation_depth_decoder.py:134-184.  PAD has no dropout of its own: its only sites are those of its two decoders
+    (``depth_dec.decoder.N...``, ``seg_dec.decoder.N...``), named by decoder_forward."""
     os_ = seg_args.get("output_stride", 1)
     dl, fl = seg_args.get("distillation_layer", 7), seg_args.get("final_layer", 9)
     side = seg_args.get("side_output", True)
@@ -447,9 +454,9 @@ def pose_decoder(c, p, feat, num_frames=2):
     return x[..., :3], x[..., 3:]
 
 
-def model_forward(sd, model_cfg, inputs, train=True, dropout=False, use_pose_net=None):
+def model_forward(sd, model_cfg, inputs, train=True, dropout=False, use_pose_net=None, drop_masks=None):
     """joint_segmentation_depth.py:77-100 (+ predict_poses :20-70, both pose_model_input modes)."""
-    c = Ctx(sd, train, dropout)
+    c = Ctx(sd, train, dropout, drop_masks)
     nl = int(model_cfg["backbone_name"].replace("resnet", ""))
     rswd = model_cfg.get("replace_stride_with_dilation")
     enc_ch = num_ch_enc(nl)

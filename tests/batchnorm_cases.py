@@ -25,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 import bn_bitmask_cases as BM
+from oracle import dropout as OD
 from improving_segmentation_with_selfsupervised_depth_amd import _lib
 from improving_segmentation_with_selfsupervised_depth_amd import functional as Fn
 from improving_segmentation_with_selfsupervised_depth_amd import hipops as H
@@ -273,8 +274,11 @@ def check_stats(group, case, xo, x, seed=0):
 
 
 def keep_mask(M, C, p, seed, device):
-    """the counter-based draw on the logical index m * C + c, as dropout_kernel makes it"""
-    keep = (H.dropout(torch.ones(M, C, dtype=torch.float32).to(device), p, seed) != 0).cpu()
+    """the counter-based draw on the logical index m * C + c, from the specification (oracle/dropout.py); the mask dropout_kernel
+    makes is a second witness that must equal it"""
+    keep = torch.from_numpy(OD.keep(seed, (M, C), p))
+    witness = (H.dropout(torch.ones(M, C, dtype=torch.float32).to(device), p, seed) != 0).cpu()
+    assert torch.equal(witness, keep), ("dropout_kernel's mask is not the specification's", int((witness != keep).sum()))
     frac = float(keep.float().mean())
     assert abs(frac - (1 - p)) <= 0.02, ("keep fraction", frac)
     return keep

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 import kernel_cases as KC
+from oracle import dropout as OD
 from improving_segmentation_with_selfsupervised_depth_amd import functional as Fn
 from improving_segmentation_with_selfsupervised_depth_amd import hipops as H
 
@@ -495,7 +496,8 @@ def run_pointwise_case(C, device, **kw):
           [x.double() * s.double().view(2, 1, 1, C)], **kw)
     sweep(case, "nhwc_to_nchw", lambda o, n: (H.nhwc_to_nchw(o["x"]),), dict(x=xd), ("x",), [KC.nchw(x).double()], **kw)
     y = H.dropout(xd, 0.3, 12345)
-    kept = (y != 0).double().cpu()
+    kept = torch.from_numpy(OD.keep(12345, tuple(x.shape), 0.3)).double()      # the specification's mask (oracle/dropout.py);
+    assert torch.equal((y != 0).double().cpu(), kept), (case, "dropout_kernel's mask is not the specification's")      # a witness
     assert 0.5 < float(kept.mean()) < 0.9
     sweep(case, "dropout", lambda o, n: (H.dropout(o["x"], 0.3, 12345),), dict(x=xd), ("x",), [x.double() * kept / (1.0 - 0.3)], **kw)
     for r in RECORDS:

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 import batchnorm_cases as BC
 import bn_bitmask_cases as BM
+from oracle import dropout as OD
 from improving_segmentation_with_selfsupervised_depth_amd import _lib
 from improving_segmentation_with_selfsupervised_depth_amd import hipops as H
 
@@ -147,8 +148,12 @@ def k_bwd_global(dyo, yo, mask, xo, mean, invstd, gamma, beta, act, p, seed, row
 
 
 def _keep(M, C, p, device):
-    """the counter-based draw on the logical index m * C + c of ONE rank's operand (each rank draws on its own rows)"""
-    return (H.dropout(torch.ones(M, C, dtype=torch.float32).to(device), p, BC.SEED) != 0).cpu()
+    """the counter-based draw on the logical index m * C + c of ONE rank's operand (each rank draws on its own rows), from the
+    specification (oracle/dropout.py); dropout_kernel's mask is a second witness that must equal it"""
+    keep = torch.from_numpy(OD.keep(BC.SEED, (M, C), p))
+    witness = (H.dropout(torch.ones(M, C, dtype=torch.float32).to(device), p, BC.SEED) != 0).cpu()
+    assert torch.equal(witness, keep), ("dropout_kernel's mask is not the specification's", int((witness != keep).sum()))
+    return keep
 
 
 def _running0(x):
