@@ -34,6 +34,12 @@ class BnFoldJob(ctypes.Structure):
         (n, c_int) for n in ("O", "I", "KH", "KW", "block0", "reserved")]
 
 
+class SegEnsView(ctypes.Structure):
+    """mirror of ``segsde_seg_ens_view`` (include/segsde_hip.h)"""
+    _fields_ = [("logits", c_void_p)] + [(n, c_long) for n in ("sb", "sc", "sh", "sw")] + [(n, c_int) for n in ("Hi", "Wi", "flip")] + [
+        ("weight", c_float)]
+
+
 class ConvDesc(ctypes.Structure):
     """mirror of ``segsde_conv_desc`` (include/segsde_hip.h)"""
     _fields_ = [(n, c_int) for n in (
@@ -210,6 +216,9 @@ _SIGS = {
     "segsde_seg_eval_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "segsde_seg_eval": (c_int, [P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int64, P, P, P, P,
                                 c_size_t, P]),
+    "segsde_seg_ens_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "segsde_seg_ens_plan": (c_int, [POINTER(SegEnsView), c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "segsde_seg_ens": (c_int, [POINTER(SegEnsView), c_int, c_int, c_int, P, c_int, c_int, c_int64, P, P, P, P, c_size_t, P]),
     "segsde_berhu_workspace": (c_size_t, [c_long]),
     "segsde_berhu_forward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, c_double, P, P, P, c_size_t, P]),
     "segsde_berhu_backward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, P, P, P, P]),

@@ -62,6 +62,20 @@ class runningScore(object):
         loss = (pair[0] / pair[1]).float() if return_loss else None
         return (loss, ids) if return_loss and return_ids else (loss if return_loss else ids)
 
+    def update_from_views(self, label_trues, views, flips=None, weights=None, return_loss=False, return_ids=False):
+        """Test-time ensembling (not in the reference, which scores one view): ``views`` is a list of logit tensors [B,C,h_k,w_k]
+        of the same images at any sizes, ``flips[k]`` marks the output of a horizontally mirrored pass, ``weights`` default to 1.
+        Each view is interpolated to the label grid, softmaxed and averaged inside ``hipops.seg_eval_ensemble`` (one launch);
+        the histogram takes the argmax of the mean probability.  ``return_loss``: the mean over the counted pixels of -log(mean
+        probability of the label), a 0-dim float32 tensor on the device, NaN when no pixel counts.  ``return_ids``: the
+        prediction as a uint8 [B,Ht,Wt] plane.  Returns None, the loss, the ids, or (loss, ids), as ``update_from_logits`` does.
+        No host synchronisation."""
+        views = [v.detach() for v in views]
+        _, pair, ids = H.seg_eval_ensemble(views, label_trues.detach(), flips=flips, weights=weights,
+                                           hist=self._hist(views[0].device), want_loss=return_loss, want_ids=return_ids)
+        loss = (pair[0] / pair[1]).float() if return_loss else None
+        return (loss, ids) if return_loss and return_ids else (loss if return_loss else ids)
+
     def get_scores(self):
         """metrics.py:27-56"""
         hist = self.confusion_matrix

@@ -2665,6 +2665,134 @@ def seg_eval(logits, gt, n_classes=None, hist=None, ignore_index=250, want_loss=
 
 
 # ----------------------------------------------------------------------------------------------
+# segmentation evaluation with test-time ensembling (csrc/segens.hip; evaluation/metrics.py::runningScore.update_from_views,
+# trainer.validate(tta=...) and inference.predict_batch(tta=...) call it)
+# ----------------------------------------------------------------------------------------------
+SEG_ENS_MAX_VIEWS = 16          # SEGSDE_SEG_ENS_MAX_VIEWS
+SEG_ENS_MAX_CLASSES = 171       # SEGSDE_SEG_ENS_MAX_CLASSES
+
+
+def _seg_ens_views(views, flips, weights):
+    """-> (float32 view tensors, flip flags, weights, B, C); everything that can be refused without the library"""
+    if not isinstance(views, (list, tuple)):
+        raise TypeError("views must be a list of [B,C,h,w] logit tensors")
+    K = len(views)
+    if K == 0:
+        raise ValueError("views is empty: at least one view is needed")
+    if K > SEG_ENS_MAX_VIEWS:
+        raise ValueError("%d views: at most %d are ensembled in one call" % (K, SEG_ENS_MAX_VIEWS))
+    for k, v in enumerate(views):
+        if not (torch.is_tensor(v) and v.dim() == 4 and v.is_floating_point()):
+            raise TypeError("views[%d] must be a floating-point [B,C,h,w] tensor" % k)
+        if min(int(s) for s in v.shape) < 1:
+            raise ValueError("views[%d] is empty: %s" % (k, tuple(v.shape)))
+        if v.shape[0] != views[0].shape[0]:
+            raise ValueError("views[%d] holds %d images, views[0] %d" % (k, v.shape[0], views[0].shape[0]))
+        if v.shape[1] != views[0].shape[1]:
+            raise ValueError("views[%d] has %d classes, views[0] %d" % (k, v.shape[1], views[0].shape[1]))
+        if v.device != views[0].device:
+            raise ValueError("views[%d] is on %s, views[0] on %s" % (k, v.device, views[0].device))
+    flips = [False] * K if flips is None else [bool(f) for f in flips]
+    if len(flips) != K:
+        raise ValueError("%d flips for %d views" % (len(flips), K))
+    weights = [1.0] * K if weights is None else [float(w) for w in weights]
+    if len(weights) != K:
+        raise ValueError("%d weights for %d views" % (len(weights), K))
+    for k, w in enumerate(weights):
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError("weights[%d] = %r: weights are finite and >= 0" % (k, w))
+        if w > 0.0 and float(np.float32(w)) in (0.0, float("inf")):
+            raise ValueError("weights[%d] = %r is not representable as a positive float32" % (k, w))
+    if not any(w > 0.0 for w in weights):
+        raise ValueError("weights %r are all zero" % (weights,))
+    B, C = int(views[0].shape[0]), int(views[0].shape[1])
+    if C > SEG_ENS_MAX_CLASSES:
+        raise NotImplementedError("%d classes: the ensemble kernel holds at most %d on chip" % (C, SEG_ENS_MAX_CLASSES))
+    lgs = [v.detach().float() for v in views]
+    return lgs, flips, weights, B, C
+
+
+def _seg_ens_descs(lgs, flips, weights):
+    descs = (_lib.SegEnsView * len(lgs))()
+    for k, lg in enumerate(lgs):
+        sb, sc, sh, sw = lg.stride()
+        descs[k] = _lib.SegEnsView(lg.data_ptr(), sb, sc, sh, sw, int(lg.shape[2]), int(lg.shape[3]), int(flips[k]), weights[k])
+    return descs
+
+
+def seg_eval_ensemble_plan(views, size, flips=None, weights=None):
+    """-> (tile rows, [route per view]): the plan ``seg_eval_ensemble`` follows for these views and the label size ``size``; a
+    route is "lds" (the tile's source footprint is staged in LDS), "direct" (taps read from memory) or None (weight 0)"""
+    lgs, flips, weights, B, C = _seg_ens_views(views, flips, weights)
+    descs = _seg_ens_descs(lgs, flips, weights)
+    staged = (ctypes.c_int * len(lgs))()
+    th = _lib.lib().segsde_seg_ens_plan(descs, len(lgs), C, int(size[0]), int(size[1]), staged)
+    check(min(th, 0), "seg_eval_ensemble_plan")
+    return th, [{1: "lds", 0: "direct"}.get(s) for s in staged]
+
+
+def seg_eval_ensemble(views, gt=None, flips=None, weights=None, size=None, n_classes=None, hist=None, ignore_index=250,
+                      want_loss=True, want_ids=False):
+    """Test-time ensembling scored at label resolution in one launch.  views: a list of 1..16 logit tensors [B,C,h_k,w_k] of the same
+    images (NCHW-logical; dense, channels-last or a slice: read in place through their strides; half precision is converted like
+    ``seg_eval`` converts it); flips[k]: view k is the network's output for the horizontally mirrored image and is mirrored back;
+    weights[k] >= 0 (default all 1).  gt int64 [B,Ht,Wt] of any size -> (hist, loss_pair, ids) like ``seg_eval``: per label pixel
+    every view is interpolated bilinearly (align_corners=True) to the label grid, turned into class probabilities by a softmax
+    and averaged with weights w_k / sum w; ``hist[C * gt + argmax] += 1`` (lowest index on a tie), the sum of -log(mean
+    probability of the label) and the pixel count over ``gt != ignore_index`` as a float64 [2], the argmax as a uint8 plane.
+    ``gt=None`` with ``size=(Ht, Wt)`` is the inference form: only the ids are computed and returned as (None, None, ids).
+
+    Exact guarantees: two calls return the same bits; a view of weight 0 is not read and the result has the bits of the call
+    without it; the weights enter only as float32(w_k / sum w) with the quotient formed in float64, so a common factor changes
+    nothing when the scaled weights and their sum are exact in float64 ([2,2,2] gives the bits of [1,1,1]; an arbitrary factor
+    need not).  The resized logits and the probabilities are never materialised; no host synchronisation."""
+    lgs, flips, weights, B, C = _seg_ens_views(views, flips, weights)
+    dev = lgs[0].device
+    if gt is None:
+        if size is None or len(size) != 2:
+            raise ValueError("without gt the label size is needed: size=(Ht, Wt)")
+        if hist is not None or n_classes is not None:
+            raise ValueError("hist and n_classes need gt: the inference form (gt=None) returns only the ids")
+        Ht, Wt = int(size[0]), int(size[1])
+        want_loss, want_ids = False, True
+    else:
+        if not (torch.is_tensor(gt) and gt.dim() == 3 and gt.dtype == torch.int64):
+            raise TypeError("gt must be an int64 [B,Ht,Wt] tensor")
+        if size is not None and tuple(int(s) for s in size) != tuple(gt.shape[1:]):
+            raise ValueError("size = %r, but gt is %s" % (size, tuple(gt.shape)))
+        if gt.shape[0] != B:
+            raise ValueError("the views hold %d images, gt %d" % (B, gt.shape[0]))
+        if gt.device != dev:
+            raise ValueError("the views are on %s, gt on %s" % (dev, gt.device))
+        Ht, Wt = int(gt.shape[1]), int(gt.shape[2])
+    if min(Ht, Wt) < 1:
+        raise ValueError("empty label grid %d x %d" % (Ht, Wt))
+    if n_classes is not None and int(n_classes) != C:
+        raise ValueError("n_classes = %d, but the views have %d classes" % (n_classes, C))
+    if hist is not None:
+        if not (torch.is_tensor(hist) and hist.dtype == torch.int64 and hist.numel() == C * C and hist.is_contiguous()):
+            raise ValueError("hist must be a contiguous int64 tensor of %d x %d elements" % (C, C))
+        if hist.device != dev:
+            raise ValueError("hist is on %s, the views on %s" % (hist.device, dev))
+    elif n_classes is not None:
+        hist = torch.zeros(C * C, dtype=torch.int64, device=dev)
+    if hist is None and not want_loss and not want_ids:
+        raise ValueError("nothing to compute: no hist (or n_classes), want_loss and want_ids are off")
+    gt = None if gt is None else gt.detach().contiguous()
+    pair = torch.empty(2, dtype=torch.float64, device=dev) if want_loss else None
+    ids = torch.empty((B, Ht, Wt), dtype=torch.uint8, device=dev) if want_ids else None
+    L = _lib.lib()
+    nb = L.segsde_seg_ens_workspace(B, Ht, Wt) if want_loss else 0
+    ws_ = _ws(nb, lgs[0]) if want_loss else None
+    descs = _seg_ens_descs(lgs, flips, weights)
+    nbytes = sum(4.0 * lg.numel() for lg, w in zip(lgs, weights) if w > 0) + B * Ht * Wt * (8.0 + (1.0 if want_ids else 0.0))
+    _timed("hbm_seg_eval_ensemble", nbytes, lgs[0], lambda: check(L.segsde_seg_ens(
+        descs, len(lgs), B, C, _p(gt), Ht, Wt, int(ignore_index), _p(hist), _p(pair), _p(ids), _p(ws_), nb, _stream(lgs[0])),
+        "seg_eval_ensemble"))
+    return hist, pair, ids
+
+
+# ----------------------------------------------------------------------------------------------
 # BerHu pseudo-depth loss (csrc/berhu.hip; loss.loss.berhu / berhu_own_car call it)
 # ----------------------------------------------------------------------------------------------
 BERHU_THRESHOLD = 0.2         # the reference's constant (loss.py:6)

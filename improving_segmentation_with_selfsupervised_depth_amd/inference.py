@@ -72,19 +72,29 @@ def colorize(img, lut, mask_zero=False, max_percentile=100):
 
 
 def predict_batch(model, monodepth_loss_calculator, inputs_val, label_colors, segmentation=True, monodepth=True, amp=False,
-                  unmapped="keep"):
+                  unmapped="keep", tta=None):
     """The body of ``Inference.run`` for one batch already on the model's device: the forward pass under ``no_grad`` and
     ``autocast(enabled=amp)``, ``generate_depth_test_pred``, then the renders.  Returns device tensors:
     ``image`` uint8 [B,H,W,3] (the input ``("color_aug", 0, 0)``), ``label`` uint8 [B,H,W,3] and ``pred_ids`` uint8 [B,H,W]
     (None without segmentation), ``depth`` uint8 [B,H,W,1] (the disparity ``("disp", 0)``; None without monodepth), and
     ``outputs``, the model's dict.  The model's mode is the caller's (the reference calls ``model.eval()`` once, before its loop);
-    ``functional.frozen_bn_fold()`` applies if the caller is inside it."""
+    ``functional.frozen_bn_fold()`` applies if the caller is inside it.
+    ``tta`` (not in the reference): ``{"scales": [...], "flip": bool, "weights": optional}`` -- ``label`` and ``pred_ids`` are
+    then the test-time ensemble of ``evaluation.tta`` at the input size (``hipops.seg_eval_ensemble`` without labels); the forward
+    pass above doubles as its (scale 1.0, not flipped) view.  ``outputs`` stays the plain pass."""
     with torch.no_grad():
         with torch.autocast(device_type="cuda", enabled=bool(amp)):
             outputs = model(inputs_val)
         result = {"outputs": outputs, "label": None, "pred_ids": None, "depth": None}
         result["image"] = render_unit_image(inputs_val[("color_aug", 0, 0)])
-        if segmentation:
+        if segmentation and tta is not None:
+            from .evaluation.tta import ensemble_forward
+            views, flips = ensemble_forward(model, inputs_val, tta["scales"], tta.get("flip", False),
+                                            base_semantics=outputs["semantics"], amp=amp)
+            size = tuple(inputs_val[("color_aug", 0, 0)].shape[-2:])
+            ids = H.seg_eval_ensemble(views, flips=flips, weights=tta.get("weights"), size=size)[2]
+            result["label"], result["pred_ids"] = H.render_labels(label_colors, ids=ids, unmapped=unmapped), ids
+        elif segmentation:
             result["label"], result["pred_ids"] = render_segmentation(semantics=outputs["semantics"], label_colors=label_colors,
                                                                       unmapped=unmapped, return_ids=True)
         if monodepth:

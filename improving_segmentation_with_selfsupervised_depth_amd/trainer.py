@@ -447,7 +447,7 @@ def train_step(model, optimizer, inputs, step, cfg, loss_fn, monodepth_loss_calc
 
 
 def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=None, loss_fn=None, running_depth=None,
-             n_imgs_to_save=None, device=None):
+             n_imgs_to_save=None, device=None, tta=None):
     """``Trainer.validate`` (train.py:817-902) as a free function over what the method reads from ``self``; no writer.
     ``val_batches``: an iterable of input dicts (the validation loader).  The model runs in ``eval()`` mode (the previous mode is
     restored on return) under ``no_grad`` and ``autocast(enabled=cfg["training"]["amp"])``.
@@ -460,6 +460,11 @@ def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=N
     ``loss.berhu_own_car``: no mask tensor, its threshold stays on the device.
     ``running_depth`` (a ``runningDepthScore``) is updated with outputs[("depth", 0, 0)] when the batch has "depth_gt".
     ``n_imgs_to_save`` defaults to ``cfg["training"]["n_tensorboard_imgs"]``.
+    ``tta`` (or ``cfg["training"]["tta"]``; not in the reference): ``{"scales": [...], "flip": bool, "weights": optional}`` -- the
+    segmentation loss, confusion matrix and saved prediction then come from the test-time ensemble of ``evaluation.tta`` scored by
+    ``runningScore.update_from_views`` (the loss is -log of the label's mean probability; a custom ``loss_fn`` is refused).  The
+    plain forward pass of the unmodified inputs still feeds the monodepth, depth-metric and BerHu parts and doubles as the
+    (scale 1.0, not flipped) view.  None: the single-view path.
 
     -> {"losses": {name: float}, "score": ..., "class_iou": ... (``runningScore.get_scores``; None without segmentation),
     "depth": ``running_depth.get_scores()`` or None, "imgs_to_save": [[img, label, pred_ids, disp], ...] (device tensors, the
@@ -472,6 +477,12 @@ def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=N
     if n_imgs_to_save is None:
         n_imgs_to_save = tr.get("n_tensorboard_imgs", 0)
     fused_loss = loss_fn is None or loss_fn is cross_entropy2d
+    if tta is None:
+        tta = tr.get("tta", None)
+    if tta is not None:
+        from .evaluation.tta import ensemble_forward
+        if not fused_loss:
+            raise ValueError("tta: the ensemble's loss is computed with its score; a custom loss_fn cannot be combined with it")
     was_training = model.training
     model.eval()
     val_loss_meter = AverageMeterDict()
@@ -495,7 +506,14 @@ def validate(model, val_batches, cfg, n_classes, monodepth_loss_calculator_val=N
                     want_ids = len(imgs_to_save) < n_imgs_to_save
                     if not fused_loss:
                         val_segmentation_loss = loss_fn(input=semantics, target=labels_val)
-                    got = running_metrics_val.update_from_logits(labels_val, semantics, return_loss=fused_loss, return_ids=want_ids)
+                    if tta is not None:
+                        views, flips = ensemble_forward(model, inputs_val, tta["scales"], tta.get("flip", False),
+                                                        base_semantics=semantics, amp=tr.get("amp", False))
+                        got = running_metrics_val.update_from_views(labels_val, views, flips=flips, weights=tta.get("weights"),
+                                                                    return_loss=True, return_ids=want_ids)
+                    else:
+                        got = running_metrics_val.update_from_logits(labels_val, semantics, return_loss=fused_loss,
+                                                                     return_ids=want_ids)
                     if fused_loss:
                         val_segmentation_loss = got[0] if want_ids else got
                     pred = (got[1] if fused_loss else got) if want_ids else [None] * images_val.shape[0]

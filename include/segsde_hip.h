@@ -848,6 +848,48 @@ int segsde_seg_eval(const float* logits, long sb, long sc, long sh, long sw, int
                     int Ht, int Wt, int64_t ignore_index, unsigned long long* hist, double* loss, unsigned char* ids,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- segmentation evaluation with test-time ensembling at label resolution, csrc/segens.hip (not in the reference, which
+ * evaluates one view).  K <= SEGSDE_SEG_ENS_MAX_VIEWS views of the same B images: view k holds float32 logits [B,C,Hi,Wi] on the
+ * device, addressed like the logits of segsde_seg_eval by four ELEMENT strides, a flip flag and a weight >= 0.  The array of
+ * descriptors is HOST memory; the call copies what it needs into the kernel arguments, so the array may be released on return.
+ * For every label pixel, views in the given order (a view of weight 0 is not read, as if it were not in the list):
+ *   z = the C logits interpolated as segsde_seg_eval interpolates them (align_corners=True, fp32); a view with flip != 0 is read
+ *   at source column Wi - 1 - i for tap column i: the network saw the mirrored image, its output is mirrored back;
+ *   p = softmax(z) in fp32: exp(z - max z) / sum;   acc[c] += float(weight / sum of the weights, formed in double) * p[c];
+ * then   argmax over acc: strict >, the lowest index wins a tie (NaN logits: unspecified);
+ *   hist[C * label + argmax] += 1                                    where 0 <= label < C          (hist: [C*C], ACCUMULATED);
+ *   loss[0] += -log(max(acc[label], FLT_MIN)), loss[1] += 1          where label != ignore_index and 0 <= label < C
+ *                                                                    (fp32 terms summed in float64; loss: double[2], OVERWRITTEN);
+ *   ids[pixel] = argmax                                              (uint8 [B,Ht,Wt]).
+ * Each of hist, loss, ids may be null (not all three); labels (dense int64 [B,Ht,Wt]) may be null when only ids are asked for.
+ * A label outside [0,C) other than ignore_index counts nowhere.  The resized logits and the probabilities are never written to
+ * memory.  One launch whatever K is (plus a one-block fold of the loss partials), no host synchronisation.  Block-private
+ * histograms with integer atomics, block partials folded in a fixed order, no float atomics: two calls give identical bits.
+ * SEGSDE_ERR_NULL: views, the logits of a view with weight > 0, all three outputs, loss without a workspace, hist or loss without
+ * labels.  SEGSDE_ERR_SHAPE: K < 1 or K > SEGSDE_SEG_ENS_MAX_VIEWS, a weight that is negative, NaN or infinite, all weights 0,
+ * Hi, Wi, B, C, Ht, Wt <= 0.  SEGSDE_ERR_UNSUPPORTED: C > SEGSDE_SEG_ENS_MAX_CLASSES (the C*C histogram and a one-row tile's
+ * accumulator no longer fit the 160 KB of LDS of a workgroup), Ht * Wt >= 2^32, more than 2^31 - 1 tiles, a workspace that is not
+ * 8-byte aligned, a device that does not grant the LDS.  SEGSDE_ERR_WORKSPACE: loss asked for and fewer than
+ * segsde_seg_ens_workspace(B, Ht, Wt) bytes.
+ * segsde_seg_ens_plan: the label rows per tile (16, 8, 4, 2 or 1; tiles are 64 pixels wide) the call would use, or an error code
+ * as above; reads Hi, Wi and weight of the descriptors only.  staged (int[K], may be null): per view 1 when the tile's source
+ * footprint is staged in LDS, 0 when its taps are read straight from memory (the footprint does not fit, or it holds more source
+ * pixels than the tile reads taps: downscaling by more than about two per axis), -1 for a view of weight 0. */
+#define SEGSDE_SEG_ENS_MAX_VIEWS 16
+#define SEGSDE_SEG_ENS_MAX_CLASSES 171
+typedef struct segsde_seg_ens_view {
+  const float* logits;
+  long sb, sc, sh, sw;
+  int Hi, Wi;
+  int flip;
+  float weight;
+} segsde_seg_ens_view;
+size_t segsde_seg_ens_workspace(int B, int Ht, int Wt);
+int segsde_seg_ens_plan(const segsde_seg_ens_view* views, int K, int C, int Ht, int Wt, int* staged);
+int segsde_seg_ens(const segsde_seg_ens_view* views, int K, int B, int C, const int64_t* labels, int Ht, int Wt,
+                   int64_t ignore_index, unsigned long long* hist, double* loss, unsigned char* ids, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ---- BerHu pseudo-depth distillation loss (loss.py:5-15; the depth loss of experiments.py:229-301 and a term of every DepthMix
  * validation, train.py:489-496, 870-878), csrc/berhu.hip.  input, target, mask: dense float32 tensors of n elements on the device
  * (mask may be null: all ones).  With apply_log, input and target are replaced by log(1 + .) first.
