@@ -1017,6 +1017,8 @@ def split_bf16(x):
 def _rows(t):
     """(M, C, ld) of an NHWC (or [M, C]) tensor"""
     if t.dim() == 2:
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError("[M, C] tensor must be channel-contiguous, got strides %s for shape %s" % (t.stride(), tuple(t.shape)))
         return t.shape[0], t.shape[1], int(t.stride(0)) if t.shape[0] > 1 else t.shape[1]
     B, H, W, C = t.shape
     return B * H * W, C, nhwc_ld(t)
@@ -1333,11 +1335,17 @@ def maxpool_backward(dy, idx, in_shape, accumulate_into=None):
     """accumulate_into: a dense tensor of in_shape that already holds another consumer's gradient of the pooled tensor: the
     result is added to it in the kernel and that tensor is returned"""
     B, H, W, C = in_shape
-    dy = dy.contiguous()
+    out_shape = (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C)
+    if idx.dtype != torch.uint8:
+        raise TypeError("idx must be uint8 (the window taps maxpool_forward returns), got %s" % idx.dtype)
+    if tuple(idx.shape) != out_shape or tuple(dy.shape) != out_shape:
+        raise ValueError("dy %s and idx %s must have the pooled shape %s of in_shape %s" % (
+            tuple(dy.shape), tuple(idx.shape), out_shape, tuple(in_shape)))
+    dy, idx = _cf32(dy, "dy"), idx.contiguous()
     acc = accumulate_into if (accumulate_into is not None and tuple(accumulate_into.shape) == tuple(in_shape)
-                              and accumulate_into.is_contiguous()) else None
+                              and accumulate_into.dtype == torch.float32 and accumulate_into.is_contiguous()) else None
     dx = acc if acc is not None else torch.empty(in_shape, dtype=torch.float32, device=dy.device)
-    check(_lib.lib().segsde_maxpool3x3s2_backward(_p(_f32(dy)), _p(idx), B, H, W, C, _p(dx), 1 if acc is not None else 0,
+    check(_lib.lib().segsde_maxpool3x3s2_backward(_p(dy), _p(idx), B, H, W, C, _p(dx), 1 if acc is not None else 0,
                                                   _stream(dy)), "maxpool_bwd")
     return dx
 
@@ -1387,29 +1395,43 @@ def gate_forward(f, a):
 
 
 def gate_backward(dy, f, a):
-    dy = dy.contiguous()
+    dy, f, a = _cf32(dy, "dy"), _cf32(f, "f"), _cf32(a, "a")
+    if dy.numel() != f.numel() or a.numel() != f.numel():
+        raise ValueError("gate_backward: dy %s, f %s and a %s differ in size" % (tuple(dy.shape), tuple(f.shape), tuple(a.shape)))
     df, da = torch.empty_like(f), torch.empty_like(a)
-    check(_lib.lib().segsde_gate_backward(_p(_f32(dy)), _p(f), _p(a), f.numel(), _p(df), _p(da), _stream(f)), "gate_bwd")
+    check(_lib.lib().segsde_gate_backward(_p(dy), _p(f), _p(a), f.numel(), _p(df), _p(da), _stream(f)), "gate_bwd")
     return df, da
 
 
-def axpby(alpha, x, beta=0.0, y=None, out=None):
-    x = x.contiguous()
+def _axpby_operands(x, y, out, what):
+    """x, y: contiguous float32 copies held by the caller; out: written in place through its address"""
+    x = _cf32(x, "x")
     if y is not None:
-        y = y.contiguous()
-    out = torch.empty_like(x) if out is None else out
-    check(_lib.lib().segsde_axpby(x.numel(), float(alpha), _p(_f32(x)), float(beta), _p(y), _p(out), _stream(x)), "axpby")
+        y = _cf32(y, "y")
+        if y.numel() != x.numel():
+            raise ValueError("%s: y %s is not of the size of x %s" % (what, tuple(y.shape), tuple(x.shape)))
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _f32(_dense(out, "out"), "out")
+        if out.numel() != x.numel():
+            raise ValueError("%s: out %s is not of the size of x %s" % (what, tuple(out.shape), tuple(x.shape)))
+    return x, y, out
+
+
+def axpby(alpha, x, beta=0.0, y=None, out=None):
+    x, y, out = _axpby_operands(x, y, out, "axpby")
+    check(_lib.lib().segsde_axpby(x.numel(), float(alpha), _p(x), float(beta), _p(y), _p(out), _stream(x)), "axpby")
     return out
 
 
 def axpby_dev(alpha_t, x, beta_t=None, y=None, out=None):
     """out = alpha_t[0]*x (+ beta_t[0]*y) with 1-element DEVICE tensors as scalars (no host sync)"""
-    x = x.contiguous()
-    if y is not None:
-        y = y.contiguous()
-    out = torch.empty_like(x) if out is None else out
-    check(_lib.lib().segsde_axpby_dev(x.numel(), _p(_f32(alpha_t)), _p(_f32(x)), _p(beta_t), _p(y), _p(out), _stream(x)),
-          "axpby_dev")
+    x, y, out = _axpby_operands(x, y, out, "axpby_dev")
+    alpha_t = _f32(alpha_t, "alpha_t")
+    if beta_t is not None:
+        beta_t = _f32(beta_t, "beta_t")
+    check(_lib.lib().segsde_axpby_dev(x.numel(), _p(alpha_t), _p(x), _p(beta_t), _p(y), _p(out), _stream(x)), "axpby_dev")
     return out
 
 
